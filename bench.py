@@ -11,8 +11,19 @@ reported as top-level value_64B / roofline_64B and value_imix / roofline_imix;
 BASELINE configs[0] (1M x 64 B through the reference's CPU loop) is
 cpu_baseline_cfg0.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it generates the
+1500 B batch, runs W warm-up and K timed steps and prints the line (`value`,
+`ms_per_step` = wall milliseconds per timed step, and the roofline of the same
+K launches by their HIP events).  --dump-outputs DIR then writes what the last
+timed step left in the output buffer (dump_outputs below); the inputs depend
+on the arguments alone, so two builds can be compared array for array.
+Everything else described here runs under --full only: the 64 B, IMIX and RSS
+batches, the checker leg, the CPU baselines, the rocprofv3 --pmc passes and
+the host-resident burst legs (--only WORKLOAD still times that one workload
+alone, with or without --full).
 
 Without a launcher, --gpus N > 1 starts torch.distributed.run with N ranks
 as a child process (before anything touches the GPU) and relays rank 0's
@@ -72,6 +83,12 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--packets", type=int, default=16 << 20, help="packets per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the 64 B / IMIX / RSS batches, check the outputs against the oracle, "
+                         "time the CPU baselines, take the PMC traffic passes and run the burst legs "
+                         "(the --no-* options below trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline workload's outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-extra", action="store_true", help="skip the 64 B / IMIX lines")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -84,7 +101,10 @@ def parse(argv=None):
     ap.add_argument("--allow-shared-devices", action="store_true",
                     help="let ranks share GPUs when WORLD_SIZE exceeds the visible devices "
                          "(rehearsals only: the line then says so)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_decision(gpus, env):
@@ -776,6 +796,33 @@ def load_traffic(key="1500", kernel=None):
     return d.get(f"bytes_per_launch_{key}")
 
 
+DUMP_PACKETS = 6 << 20     # two float32 arrays of 24 MiB
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: the arrays a caller of the headline workload receives,
+    as its last timed step left them (every step writes the same output
+    buffer, downloaded once after the timed region): one u32 per packet,
+    ip_cksum in the low half and tcp_cksum in the high half, written as
+    <path>/ip_cksum_<workload>.npy and tcp_cksum_<workload>.npy in float32
+    (16-bit values, exact).  A batch above DUMP_PACKETS packets is sampled:
+    DUMP_PACKETS distinct packets in ascending order, drawn with SEED, so the
+    same packets in every run.  An RSS-only run writes the 4096 hashes of
+    its parity sample as rss_hash.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    key = next((k for k in ("1500", "64", "imix") if k in res), None)
+    if key is None:
+        arrays = {"rss_hash": res["rss"]["hash_sample"][1]}
+    else:
+        o = res[key]["out"][0] if key == "imix" else res[key]["out"]
+        if len(o) > DUMP_PACKETS:
+            o = o[np.sort(np.random.default_rng(SEED).choice(len(o), DUMP_PACKETS, replace=False))]
+        arrays = {f"ip_cksum_{key}": o & 0xFFFF, f"tcp_cksum_{key}": o >> 16}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+
+
 def roofline(n, size, ev_ms, kernel, traffic_key, extra_bytes=0, live=None):
     """HBM roofline of one workload's kernel: algorithmic bytes per launch
     (n x (L + 4) [+ descriptors]) over its HIP-event time per launch.
@@ -811,22 +858,26 @@ def main():
     plan = shard_plan(dist.rank, dist.world, args.packets)
     n = plan["n"]
     res = {}
+    only = args.only or (None if args.full else "1500")   # a plain run times the headline workload alone
 
-    if args.only in (None, "1500"):
+    if only in (None, "1500"):
         wall, ev_ms, o, k = bench_strided(torch, dist, eng, cgck, n, 1500, plan, args.steps, args.warmup)
         res["1500"] = {"wall": wall, "ev": ev_ms, "out": o, "kernel": k}
-    if not args.no_extra and args.only in (None, "64"):
+    if not args.no_extra and only in (None, "64"):
         wall, ev_ms, o, k = bench_strided(torch, dist, eng, cgck, n, 64, plan, args.steps, args.warmup)
         res["64"] = {"wall": wall, "ev": ev_ms, "out": o, "kernel": k}
-    if not args.no_extra and args.only in (None, "imix"):
+    if not args.no_extra and only in (None, "imix"):
         wall, ev_ms, nbytes, o, k, unh, ring = bench_imix(torch, dist, eng, cgck, n, plan, args.steps, args.warmup)
         res["imix"] = {"wall": wall, "ev": ev_ms, "bytes": nbytes, "out": o, "kernel": k, "unhinted": unh,
                        "ring": ring}
-    if not args.no_rss and args.only in (None, "rss"):
+    if not args.no_rss and only in (None, "rss"):
         res["rss"] = bench_rss(torch, dist, eng, cgck, plan, args.steps, args.warmup)
 
+    if args.dump_outputs and dist.rank == 0:   # rank 0's shard
+        dump_outputs(args.dump_outputs, res)
+
     # every rank checks its own shard; the totals are summed over ranks
-    par = checker_leg(res, plan, cgck)
+    par = checker_leg(res, plan, cgck) if args.full else {}
     parity = {k: {"checked": int(dist.sum(v[0])), "mismatches": int(dist.sum(v[1])), "ranks": dist.world}
               for k, v in sorted(par.items())}
     devices = dist.gather({"rank": dist.rank, "local_rank": dist.local, "device": dev,
@@ -834,12 +885,12 @@ def main():
                            if hasattr(torch.cuda.get_device_properties(dev), "pci_bus_id") else None})
 
     burst = loop = workers = None
-    if dist.rank == 0 and dist.world == 1 and not args.no_burst and args.only is None:
+    if args.full and dist.rank == 0 and dist.world == 1 and not args.no_burst and only is None:
         burst = bench_burst()
         loop = bench_loop()
         workers = bench_workers()
     cpu = cpu_r = cpu_64 = cpu_b = None
-    if dist.rank == 0 and dist.world == 1 and not args.no_cpu:
+    if args.full and dist.rank == 0 and dist.world == 1 and not args.no_cpu:
         if burst:
             cpu_b = cpu_burst()
         cpu = cpu_baseline(args.cpu_seconds)
@@ -848,7 +899,7 @@ def main():
         if "rss" in res:
             cpu_r = cpu_rss(min(3.0, args.cpu_seconds))
     live = {}
-    if dist.rank == 0 and dist.world == 1 and not args.no_pmc:
+    if args.full and dist.rank == 0 and dist.world == 1 and not args.no_pmc:
         kern = {k: res[k]["kernel"] for k in ("1500", "64", "imix") if k in res}
         if "imix" in res:
             kern["ring"] = res["imix"]["ring"]["kernel"]
@@ -903,7 +954,8 @@ def main():
                 rg["traffic_over_algorithmic"] = live["ring"] / (r["bytes"] + 16 * n)
                 rg["hbm_frac"] = live["ring"] / (rg["kernel_ms"] * 1e-3) / HBM_PEAK
                 rg["traffic_source"] = TRAFFIC_LIVE
-        out["parity"] = parity
+        if args.full:
+            out["parity"] = parity
         if cpu:
             out["cpu_baseline"] = cpu
         if cpu_64:
@@ -946,10 +998,13 @@ def main():
         if "value" not in out:   # --only 64 / imix / rss profiling runs
             if "value_64B" in out:
                 out["value"], out["config"] = out["value_64B"], {"workload": "64B"}
+                out["ms_per_step"] = out["ms_per_step_64B"]
             elif "value_imix" in out:
                 out["value"], out["config"] = out["value_imix"], {"workload": "imix"}
+                out["ms_per_step"] = out["ms_per_step_imix"]
             else:
                 out["value"], out["config"] = extra["rss_hash"]["gtuple_s"], {"workload": "rss_hash"}
+                out["ms_per_step"] = res["rss"]["hash"][0] / K * 1e3
         print(json.dumps(out), flush=True)
     eng.close()
     dist.close()

@@ -328,5 +328,28 @@ def rss_main():
     print("rss fixtures written to", HERE)
 
 
+def differential_main():
+    """differential.json: what the reference's own build returns for the
+    seeded differential cases of the CPU suite (tests/refcases.py), so those
+    tests hold the restatement to the reference where oracle/_ref is absent."""
+    sys.path[:0] = [os.path.dirname(HERE), os.path.join(ROOT, "con-gen_amd")]   # tests/, the cgck binding
+    import refcases
+    R, RR = oracle.reference(), oracle.reference_rss()
+    if R is None or RR is None:
+        sys.exit("make_golden: oracle/_ref missing (run make -C oracle)")
+    P = oracle.port()
+    a, b = refcases.cksum_random(R)
+    t, r = refcases.rss_random(RR, RR.key)
+    out = {"cksum_random": {"in_cksum": a, "udp_cksum": b},
+           "rss_random": {"toeplitz_hash": t, "rss_hash4": r},
+           "rx_replays": [refcases.digest(x) for x in refcases.rx_replays(P, R)],
+           "rsp_replay": refcases.digest(np.asarray(x) for x in refcases.rsp_replay(P, R)[:5])}
+    with open(os.path.join(HERE, "differential.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print("differential fixtures written to", HERE)
+
+
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "rss":
     rss_main()
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "differential":
+    differential_main()

@@ -18,6 +18,7 @@ import pytest
 
 import cgck
 import oracle
+import refcases
 import rxcorpus
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,19 +101,19 @@ def test_replay_policy_rules(port):
 def test_replay_reference_vs_restatement(port):
     """The same replay with the reference's in_cksum/udp_cksum (oracle/_ref)
     and with the restatement: identical outcomes, counters and bytes over a
-    corpus of every edge shape."""
+    corpus of every edge shape.  The reference's side is the digest recorded
+    from its build (tests/golden/differential.json) and, where the build is
+    present, the live run."""
+    g = refcases.golden()["rx_replays"]
+    bs = refcases.rx_replays(port, port)
     R = oracle.reference()
-    if R is None:
-        pytest.skip("reference build absent (oracle/_ref)")
-    rng = np.random.default_rng(11)
-    frames = rxcorpus.corpus(rng, R, 600)
-    for stack in (0, 1):
-        for ip_in, tcp_in in ((0, 0), (1, 1), (2, 2), (1, 2), (2, 1)):
-            a = replay(port, R.fn_pointers(), frames, stack, ip_in, tcp_in)
-            b = replay(port, port.fn_pointers(), frames, stack, ip_in, tcp_in)
-            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
-            if ip_in and tcp_in:
-                assert a[1][4] > 0 and a[1][5] > 0
+    as_ = refcases.rx_replays(port, R) if R is not None else bs
+    assert len(bs) == len(g) == len(refcases.RX_CONFIGS)
+    for (stack, ip_in, tcp_in), a, b, want in zip(refcases.RX_CONFIGS, as_, bs, g):
+        assert refcases.digest(b) == want, (stack, ip_in, tcp_in)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+        if ip_in and tcp_in:
+            assert b[1][4] > 0 and b[1][5] > 0
 
 
 def _run(code):
@@ -175,35 +176,19 @@ def rsp_replay(port, fns, buf, desc, tx_base, tx_stride, cap, ip_in, tcp_in, ka=
     return res, ctr, txs, idn, local
 
 
-def keepalives(rng, n):
-    ka = np.zeros(n, P.KA_DTYPE)
-    ka["laddr"] = rng.integers(0, 2 ** 32, n, dtype=np.uint64)
-    ka["faddr"] = rng.integers(0, 2 ** 32, n, dtype=np.uint64)
-    ka["lport"] = rng.integers(0, 2 ** 16, n)
-    ka["fport"] = rng.integers(0, 2 ** 16, n)
-    ka["rcv_nxt"] = rng.integers(0, 2 ** 32, n, dtype=np.uint64)
-    ka["snd_una"] = rng.integers(0, 2 ** 32, n, dtype=np.uint64)
-    ka["hiwat"] = rng.integers(0, 2 ** 20, n)
-    ka["scale"] = rng.integers(0, 9, n)
-    return ka
-
-
 def test_rsp_replay_reference_vs_restatement(port):
     """The response replay over the reference's own in_cksum / udp_cksum and
     over the restatement: outcomes, counters, replies sent and every byte of
     both rings equal; every reply carries checksums that verify."""
+    b = refcases.rsp_replay(port, port)
+    b_buf, tx_base, tx_stride = b[4:]
+    # the reference's side: the digest recorded from its build, and the live run where it is present
+    assert refcases.digest(np.asarray(x) for x in b[:5]) == refcases.golden()["rsp_replay"]
     R = oracle.reference()
-    if R is None:
-        pytest.skip("reference build absent")
-    rng = np.random.default_rng(81)
-    frames = rxcorpus.rsp_corpus(rng, R, 600)
-    buf, desc, tx_base, tx_stride = rxcorpus.pool(frames, 700)
-    ka = keepalives(rng, 20)
-    a = rsp_replay(port, R.fn_pointers(), buf.copy(), desc, tx_base, tx_stride, 700, 1, 1, ka)
-    b_buf = buf.copy()
-    b = rsp_replay(port, port.fn_pointers(), b_buf, desc, tx_base, tx_stride, 700, 1, 1, ka)
-    for x, y in zip(a[:4], b[:4]):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
+    if R is not None:
+        a = refcases.rsp_replay(port, R)
+        for x, y in zip(a[:5], b[:5]):
+            assert np.array_equal(np.asarray(x), np.asarray(y))
     txs = b[2]
     assert txs[1] == 0 and txs[0] == txs[2:].sum()
     assert min(txs[2:]) > 0, txs                      # RSTs, ICMP errors, echo replies, keepalives

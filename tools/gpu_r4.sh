@@ -2,7 +2,7 @@
 #   tests   — the whole -m gpu suite (slow ones included)
 #   quick   — the burst / window tests only
 #   txburst — tools/txburst 0.2 (all burst rows, pipelined included)
-#   bench   — python bench.py (default N=1 line)
+#   bench   — python bench.py --full (the whole N=1 line)
 #   stress  — tools/reg_stress.py 60 plain
 # Each step has its own time limit; the script stops at the first failure.
 cd $GRAFT_REPO_ROOT
@@ -32,9 +32,9 @@ for step in "$@"; do
 		LD_LIBRARY_PATH=$PWD/tools/labso CGCK_TX_KSTORE=1 run txburst_kstore 400 tools/txburst 0.2 || exit 1 ;;
 	txtouch) # the TX rows with each frame's line written by the core before the clock starts
 		TXBURST_PRETOUCH=1 run txburst_pretouch 400 tools/txburst 0.2 || exit 1 ;;
-	bench) run bench 600 python -u bench.py || exit 1 ;;
+	bench) run bench 600 python -u bench.py --full || exit 1 ;;
 	smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" || exit 1 ;;
-	bench2) run bench_n2 600 python -u bench.py --gpus 2 --allow-shared-devices --steps 5 --warmup 2 --no-burst || exit 1 ;;
+	bench2) run bench_n2 600 python -u bench.py --full --gpus 2 --allow-shared-devices --steps 5 --warmup 2 --no-burst || exit 1 ;;
 	stress) run stress 110 python -u tools/reg_stress.py 60 plain || exit 1 ;;
 	stressm) for m in heap plain lock mmap; do run stress_$m 110 python -u tools/reg_stress.py 40 $m || exit 1; done ;;
 	stress3) run stress_r3 110 python -u tools/reg_stress.py 30 plain tools/r3lib/libcgck.so || exit 1

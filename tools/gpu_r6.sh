@@ -2,7 +2,7 @@
 #   tests   — the whole -m gpu suite (slow ones included)
 #   quick   — the burst / window tests only
 #   txburst — tools/txburst 0.2 (all burst rows, pipelined included)
-#   bench   — python bench.py (default N=1 line)
+#   bench   — python bench.py --full (the whole N=1 line)
 #   stress  — tools/reg_stress.py 60 plain
 # Each step has its own time limit; the script stops at the first failure.
 cd $GRAFT_REPO_ROOT
@@ -83,9 +83,9 @@ for step in "$@"; do
 		LD_LIBRARY_PATH=$PWD/tools/labso CGCK_TX_KSTORE=1 run txburst_kstore 400 tools/txburst 0.2 || exit 1 ;;
 	txtouch) # the TX rows with each frame's line written by the core before the clock starts
 		TXBURST_PRETOUCH=1 run txburst_pretouch 400 tools/txburst 0.2 || exit 1 ;;
-	bench) run bench 600 python -u bench.py || exit 1 ;;
+	bench) run bench 600 python -u bench.py --full || exit 1 ;;
 	smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" || exit 1 ;;
-	bench2) run bench_n2 600 python -u bench.py --gpus 2 --allow-shared-devices --steps 5 --warmup 2 --no-burst || exit 1 ;;
+	bench2) run bench_n2 600 python -u bench.py --full --gpus 2 --allow-shared-devices --steps 5 --warmup 2 --no-burst || exit 1 ;;
 	stress) # mmap'd rings: numpy's own allocations can come from the brk heap,
 		# which cgck_host_register refuses
 		run stress 110 python -u tools/reg_stress.py 60 mmap || exit 1 ;;
@@ -226,7 +226,7 @@ for step in "$@"; do
 	workers4) TXLOOP_WORKERS=1,8,12,16,32 run workers 600 tools/txloop 0.3 || exit 1 ;;
 	vramdb) run vramdb 120 tools/vramdb 0.3 || exit 1 ;;
 	shards) run shards 600 python -u -m pytest tests/test_gpu_shards.py -m gpu -x -v -s --timeout 500 --timeout-method thread || exit 1 ;;
-	profbench) BENCH_ARGS="--steps 10 --warmup 3 --no-cpu --no-pmc --no-burst" bash tools/gpu_prof.sh || exit 1 ;;
+	profbench) BENCH_ARGS="--full --steps 10 --warmup 3 --no-cpu --no-pmc --no-burst" bash tools/gpu_prof.sh || exit 1 ;;
 	prof) bash tools/gpu_prof_layouts.sh $(basename $O)/prof || exit 1 ;;
 	*) echo "unknown step $step"; exit 2 ;;
 	esac

@@ -7,7 +7,7 @@ doubled; WRITE_SIZE (KB) is exact for 16-B/lane streaming stores.
 
     python tools/pmc_traffic.py gpurun_out/prof_fetch gpurun_out/prof_write OUT.json [BENCH.json]
 
-With BENCH.json (a bench.py line) the kernel of each workload is the one the
+With BENCH.json (a bench.py --full line) the kernel of each workload is the one the
 dispatcher reported in that run (roofline*.kernel, extra.*.kernel).
 """
 import csv
