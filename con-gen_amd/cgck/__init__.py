@@ -29,6 +29,7 @@ STORE = 1 << 5
 VERIFY = 1 << 6
 V_IP_ZERO_IS_FFFF = 1 << 7
 V_UDP_ZERO_SKIP = 1 << 8
+IP6 = 1 << 9            # the record at l3_off is an IPv6 header (include/cgck.h, CGCK_IP6)
 GEN_BOTH = IP | L4
 FILL_BOTH = IP | L4 | ZERO_FIELDS | STORE
 VERIFY_BSD = IP | L4 | VERIFY | V_IP_ZERO_IS_FFFF | V_UDP_ZERO_SKIP
@@ -71,7 +72,7 @@ EXPORTS = (
     "cgck_rx_post", "cgck_rx_begin_posted", "cgck_tx_post", "cgck_tx_complete",
     "cgck_rx_pending", "cgck_rx_ready", "cgck_tx_pending", "cgck_tx_ready",
     "cgck_window_stats_n", "cgck_thread_bind", "cgck_thread_device",
-    "cgck_test_burst_seq", "cgck_test_burst_stale",
+    "cgck_test_burst_seq", "cgck_test_burst_stale", "cgck_synth_strided_ip6",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -127,6 +128,8 @@ def bind(path):
     L.cgck_host_register.argtypes = [_vp, ctypes.c_size_t]
     L.cgck_host_unregister.argtypes = [_vp]
     L.cgck_synth_strided.argtypes = [_vp, _vp, _u64, _u64, _u32, _u64, _vp]
+    if hasattr(L, "cgck_synth_strided_ip6"):   # IPv6 addition (an older build loads without it)
+        L.cgck_synth_strided_ip6.argtypes = [_vp, _vp, _u64, _u64, _u32, _u32, _u64, _vp]
     L.cgck_synth_imix.argtypes = [_vp, _vp, _vp, _u64, _u64, _vp]
     L.cgck_synth_imix_ring.argtypes = [_vp, _vp, _vp, _u64, _u64, _u32, _u64, _vp]
     L.cgck_imix_bytes.restype = _u64
@@ -501,6 +504,12 @@ class Engine:
     def synth_strided(self, base, n, stride, ip_len, seed, stream=None):
         _check(load().cgck_synth_strided(self.ctx, base, n, stride, ip_len, seed, stream),
                "cgck_synth_strided")
+
+    def synth_strided_ip6(self, base, n, stride, ip_len, nh, seed, stream=None):
+        """cgck_synth_strided_ip6: the synth_strided byte stream stamped as IPv6
+        packets of next header nh (its checksum field zeroed)."""
+        _check(load().cgck_synth_strided_ip6(self.ctx, base, n, stride, ip_len, nh, seed, stream),
+               "cgck_synth_strided_ip6")
 
     def synth_imix(self, base, desc, n, seed, stream=None):
         _check(load().cgck_synth_imix(self.ctx, base, desc, n, seed, stream), "cgck_synth_imix")

@@ -240,14 +240,22 @@ static inline hipStream_t pick(cgck_ctx *c, void *stream)
 // Device-resident batches
 // --------------------------------------------------------------------------
 
-static int check_flags(uint32_t flags)
+// *flags comes back as the kernels take it: RAW | IP6 is RAW (a raw region
+// has no header semantics of either family).
+static int check_flags(uint32_t *flagsp)
 {
+	const uint32_t flags = *flagsp;
 	const uint32_t known = CGCK_RAW | CGCK_IP | CGCK_L4 | CGCK_L4_NOPSEUDO | CGCK_ZERO_FIELDS |
-			       CGCK_STORE | CGCK_VERIFY | CGCK_V_IP_ZERO_IS_FFFF | CGCK_V_UDP_ZERO_SKIP;
+			       CGCK_STORE | CGCK_VERIFY | CGCK_V_IP_ZERO_IS_FFFF | CGCK_V_UDP_ZERO_SKIP | CGCK_IP6;
 	if (flags & ~known)
 		return set_err(-EINVAL, "cgck: unknown flag bits 0x%x", flags & ~known);
-	if ((flags & CGCK_RAW) && (flags & ~CGCK_RAW))
+	if ((flags & CGCK_RAW) && (flags & ~(CGCK_RAW | CGCK_IP6)))
 		return set_err(-EINVAL, "cgck: the RAW flag excludes every other flag");
+	if ((flags & CGCK_IP6) && (flags & CGCK_L4_NOPSEUDO))
+		return set_err(-EINVAL, "cgck: CGCK_L4_NOPSEUDO has no meaning with CGCK_IP6 (every IPv6 upper-layer "
+					"checksum covers the pseudo-header)");
+	if (flags & CGCK_RAW)
+		*flagsp = CGCK_RAW;
 	if (!(flags & (CGCK_RAW | CGCK_IP | CGCK_L4)))
 		return set_err(-EINVAL, "cgck: flags select no checksum (RAW, IP or L4)");
 	return 0;
@@ -272,9 +280,11 @@ extern "C" int cgck_strided(cgck_ctx_t *c, void *base, uint64_t n, uint64_t stri
 {
 	if (!c)
 		return set_err(-EINVAL, "cgck_strided: NULL context");
-	int rc = check_flags(flags);
+	int rc = check_flags(&flags);
 	if (rc)
 		return rc;
+	if ((flags & CGCK_IP6) && ip_len > 65535)
+		return set_err(-EINVAL, "cgck_strided: CGCK_IP6 takes ip_len <= 65535 (no jumbograms)");
 	if (n && !base)
 		return set_err(-EINVAL, "cgck_strided: NULL base");
 	if (ip_len > 0x7fffffffu)
@@ -288,7 +298,7 @@ extern "C" int cgck_desc(cgck_ctx_t *c, void *base, const cgck_desc_t *desc, uin
 {
 	if (!c)
 		return set_err(-EINVAL, "cgck_desc: NULL context");
-	int rc = check_flags(flags);
+	int rc = check_flags(&flags);
 	if (rc)
 		return rc;
 	if (n && (!base || !desc))
@@ -964,7 +974,9 @@ static int desc_host_impl(cgck_ctx *c, void *base, size_t bytes, const cgck_desc
 	// on the poster's thread.
 	const bool store = flags & CGCK_STORE;
 	const bool in_place = dev_base && (store || pend || burst_layout(pkt_bytes, n).bytes > kServerCopy);
-	if ((in_place || !store) && burst_fits(c, n, max_len, in_place ? 0 : pkt_bytes, pkt_bytes)) {
+	// (an IPv6 batch takes the launch path: the server's bodies are IPv4)
+	if (!(flags & CGCK_IP6) && (in_place || !store) &&
+	    burst_fits(c, n, max_len, in_place ? 0 : pkt_bytes, pkt_bytes)) {
 		// the resident server: no launch, no stream sync
 		const BurstLayout L = burst_layout(in_place ? 0 : pkt_bytes, n);
 		uint8_t *h;
@@ -1115,7 +1127,7 @@ extern "C" int cgck_desc_host(cgck_ctx_t *c, void *base, size_t bytes, const cgc
 {
 	if (!c)
 		return set_err(-EINVAL, "cgck_desc_host: NULL context");
-	int rc = check_flags(flags);
+	int rc = check_flags(&flags);
 	if (rc)
 		return rc;
 	return desc_host(c, base, bytes, desc, n, flags, out, verdict);
@@ -1130,9 +1142,13 @@ extern "C" int cgck_burst_request(cgck_ctx_t *c, const void *dev_base, uint64_t 
 {
 	if (!c && !(c = thread_ctx()))
 		return -ENODEV; // thread_ctx set the message
-	int rc = check_flags(flags);
+	const bool ip6 = flags & CGCK_IP6;
+	int rc = check_flags(&flags);
 	if (rc)
 		return rc;
+	if (ip6)
+		return set_err(-EINVAL, "cgck_burst_request: the burst server has no IPv6 bodies (CGCK_IP6): use "
+					"cgck_desc_host, which launches such a batch");
 	if (!dev_base || !range || (n && !desc))
 		return set_err(-EINVAL, "cgck_burst_request: NULL base, zero range or NULL descriptors");
 	if (n == 0)
@@ -1880,6 +1896,22 @@ extern "C" int cgck_synth_strided(cgck_ctx_t *c, void *base, uint64_t n, uint64_
 	hipStream_t st = pick(c, stream);
 	HIP_TRY(launch_synth_fill((uint8_t *)base, n * stride, seed, c->num_cus, st));
 	HIP_TRY(launch_synth_stamp((uint8_t *)base, n, stride, ip_len, c->num_cus, st));
+	return 0;
+}
+
+extern "C" int cgck_synth_strided_ip6(cgck_ctx_t *c, void *base, uint64_t n, uint64_t stride, uint32_t ip_len,
+				      uint32_t nh, uint64_t seed, void *stream)
+{
+	if (!c || (n && !base))
+		return set_err(-EINVAL, "cgck_synth_strided_ip6: bad arguments");
+	if (ip_len < 40 || ip_len > stride || ip_len > 65535 || nh > 255)
+		return set_err(-EINVAL, "cgck_synth_strided_ip6: need 40 <= ip_len <= min(stride, 65535), nh <= 255");
+	if ((uintptr_t)base & 15)
+		return set_err(-EINVAL, "cgck_synth_strided_ip6: base must be 16-byte aligned");
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = pick(c, stream);
+	HIP_TRY(launch_synth_fill((uint8_t *)base, n * stride, seed, c->num_cus, st));
+	HIP_TRY(launch_synth_stamp6((uint8_t *)base, n, stride, ip_len, nh, c->num_cus, st));
 	return 0;
 }
 

@@ -568,4 +568,120 @@ __device__ __forceinline__ void eat(Part &pt, uint4 w, int k, int q, int len, in
 		pt.tot = msum16(w, cmask16(co, q, q + len), pt.tot);
 }
 
+// --------------------------------------------------------------------------
+// IPv6 (CGCK_IP6): the extension-header walk and the group kernel's sums
+// --------------------------------------------------------------------------
+
+constexpr int kV6Ok = 0, kV6NoL4 = 1, kV6BadLen = 2;
+constexpr int kV6MaxExt = 8; // extension headers walked; one more is BAD_LEN
+
+__host__ __device__ __forceinline__ bool v6_is_ext(uint32_t nh)
+{
+	return nh == 0 || nh == 43 || nh == 60 || nh == 51;
+}
+
+// Offset of the checksum field in the upper-layer header of protocol nh
+// (TCP, UDP, ICMPv6); -1: the protocol has none.
+__host__ __device__ __forceinline__ int v6_field(uint32_t nh)
+{
+	return nh == 6 ? 16 : nh == 17 ? 6 : nh == 58 ? 2 : -1;
+}
+
+// Where the upper-layer header of an IPv6 packet of `len` bytes at `a0`
+// starts (include/cgck.h, CGCK_IP6): Hop-by-Hop, Routing and Destination
+// Options advance by (b[1] + 1) * 8, AH by (b[1] + 2) * 4; a Fragment header
+// ends the walk without an L4 result; anything else is the terminal nh.
+// st: kV6Ok, kV6NoL4 (Fragment) or kV6BadLen (len < 40, a header or the
+// checksum field past len, a ninth extension header).  nh0 = header byte 6.
+struct V6 {
+	int l4_off;
+	uint32_t nh;
+	int st;
+};
+
+__device__ __forceinline__ V6 v6_walk(uint64_t a0, int len, uint32_t nh0)
+{
+	V6 r = {40, nh0, kV6Ok};
+	if (len < 40) {
+		r.st = kV6BadLen;
+		return r;
+	}
+	for (int i = 0;; ++i) {
+		if (r.l4_off > len) {
+			r.st = kV6BadLen;
+			return r;
+		}
+		if (r.nh == 44) {
+			r.st = kV6NoL4;
+			return r;
+		}
+		if (!v6_is_ext(r.nh))
+			break;
+		if (i == kV6MaxExt || r.l4_off + 2 > len) {
+			r.st = kV6BadLen;
+			return r;
+		}
+		const uint32_t next = *gbl_at<const uint8_t>(a0 + r.l4_off);
+		const uint32_t hl = *gbl_at<const uint8_t>(a0 + r.l4_off + 1);
+		r.l4_off += r.nh == 51 ? (int)(hl + 2) * 4 : (int)(hl + 1) * 8;
+		r.nh = next;
+	}
+	const int fo = v6_field(r.nh);
+	if (fo >= 0 && r.l4_off + fo + 2 > len)
+		r.st = kV6BadLen;
+	return r;
+}
+
+// An IPv6 frame's result in the fast families (dstr6, lpd6 / lpa6), which sum
+// whole frames: with no extension header the L4 sum is the sum of bytes
+// [8, len) plus htons(len - 40) and nh << 8, so from tot = the folded sum of
+// [0, len) and h8 = that of [0, 8) it is tot - h8 plus the two constants.  A
+// frame with extension headers (even lengths, so no byte swap) is walked from
+// global memory by its lane, the words of [40, l4_off) subtracted too and the
+// length constant replaced: exact, only slower.  a0 is 4-byte aligned (the
+// families' precondition); flags hold IP / L4 only.  *verdict: 0 or BAD_LEN.
+__device__ __forceinline__ uint32_t v6_dense(uint64_t a0, int len, uint32_t tot, uint32_t h8, uint32_t nh0,
+					     uint32_t flags, uint32_t *verdict)
+{
+	*verdict = 0;
+	if (len < 40) {
+		*verdict = CGCK_BAD_LEN;
+		return 0;
+	}
+	if (!(flags & CGCK_L4))
+		return 0;
+	const V6 v = v6_walk(a0, len, nh0); // no load unless nh0 is an extension header
+	if (v.st == kV6BadLen)
+		*verdict = CGCK_BAD_LEN;
+	if (v.st != kV6Ok)
+		return 0;
+	uint32_t ext = 0; // at most 16 Ki dwords of two halves each: no overflow
+	for (int o = 40; o < v.l4_off; o += 4)
+		ext = hsum(*gbl_at<const uint32_t>(a0 + o), ext);
+	uint32_t L = ocsub(ocsub(tot, h8), fold16(ext));
+	L = fold16(L + (v.nh << 8) + bswap16((uint32_t)(len - v.l4_off) & 0xffffu));
+	return finish(L) << 16;
+}
+
+// eat() for an IPv6 packet: tot = sum over [l4, len) (the upper-layer
+// region itself: an extension chain may be longer than any header zone), ps =
+// sum over [8, 40) (src and dst of the pseudo-header), fld's high half = the
+// stored checksum field at fa (packet-relative, -1: none), read as zero.
+template <bool HDR>
+__device__ __forceinline__ void eat6(Part &pt, uint4 w, int k, int q, int len, int l4, int fa, uint32_t flags)
+{
+	const int co = k * 16;
+	if ((flags & (CGCK_VERIFY | CGCK_ZERO_FIELDS)) && fa >= 0) {
+		const uint32_t mg = cmask16(co, q + fa, q + fa + 2);
+		pt.fld += msum16(w, mg, 0) << 16;
+		zero16(w, mg);
+	}
+	if (HDR && co < q + 48)
+		pt.ps = msum16(w, cmask16(co, q + 8, q + 40), pt.ps);
+	if (co >= q + l4 && co + 16 <= q + len)
+		pt.tot = sum4(w, pt.tot);
+	else
+		pt.tot = msum16(w, cmask16(co, q + l4, q + len), pt.tot);
+}
+
 } // namespace cgck

@@ -42,6 +42,7 @@ hipError_t launch_slot2(const KParams &p, int num_cus, bool nt, hipStream_t st);
 hipError_t launch_lpa(const KParams &p, int num_cus, bool nt, hipStream_t st);
 hipError_t launch_lpd(const KParams &p, int num_cus, hipStream_t st);
 bool lpd_ok(const KParams &p);
+bool lane6_ok(const KParams &p);
 hipError_t launch_lpw(const KParams &p, int num_cus, hipStream_t st);
 bool lpw_ok(const KParams &p);
 hipError_t launch_dstr(const KParams &p, int num_cus, hipStream_t st);
@@ -77,6 +78,9 @@ hipError_t launch_slotd(const KParams &p, int num_cus, hipStream_t st);
 //     LDS-DMA (slotd).  A variant this build lacks falls back to the automatic
 //     choice; one whose preconditions a batch fails falls back to lpa, lpp or
 //     group;
+//   A CGCK_IP6 batch goes only to a family with an IPv6 variant: dstr (dstr6),
+//   lpd / lpa (lpd6, lpa6: IP / L4 flags only, lane6_ok) and group (cksum6, the
+//   full semantics); any other choice, automatic or pinned, falls back to group;
 //   kNT (bit 4) nontemporal loads, kContig (bit 5) contiguous block ranges,
 //   kExplicit (bit 6) take bits 4-5 as given instead of the measured defaults,
 //   kPacked (bit 7) the context's layout hint says packed (cgck_set_desc_layout).
@@ -87,9 +91,10 @@ hipError_t launch_cksum(const KParams &p0, uint32_t len_hint, int num_cus, int k
 		return hipSuccess;
 	KParams p = p0;
 	const bool lane_ok = !(p.flags & (kFlagNoLenCheck | kFlagL4Auto | kFlagRx | kFlagGroup));
+	const bool ip6 = p.flags & CGCK_IP6;
 	int variant = kernel & 15;
 	// aligned fixed-length strided batch of 20..64-byte packets (the 64 B config)
-	const bool lpa_ok = lane_ok && !p.desc && p.ip_len >= 20 && p.ip_len <= 64 &&
+	const bool lpa_ok = lane_ok && (!ip6 || lane6_ok(p)) && !p.desc && p.ip_len >= 20 && p.ip_len <= 64 &&
 			    ((reinterpret_cast<uintptr_t>(p.base) | p.stride | p.l3_off) & 15) == 0;
 #if CGCK_LAB
 	const bool known = variant <= 15;
@@ -112,10 +117,12 @@ hipError_t launch_cksum(const KParams &p0, uint32_t len_hint, int num_cus, int k
 			: len_hint <= kLppUpToLen ? 2 : stream ? 15 : 9;
 	if (variant >= 2 && !lane_ok)
 		variant = 1;
+	if (ip6 && variant != 10 && variant != 11 && variant != 13) // lpp, slot2, lpw (and the lab's) are IPv4 only
+		variant = 1;
 	if (variant == 10 && !lpa_ok)
-		variant = 2;
+		variant = ip6 ? 1 : 2;
 	if (variant == 13 && !(lpa_ok && lpd_ok(p)))
-		variant = lpa_ok ? 10 : 2;
+		variant = lpa_ok ? 10 : ip6 ? 1 : 2;
 #if CGCK_LAB
 	if (variant == 12 && !span_ok(p))
 		variant = 1;

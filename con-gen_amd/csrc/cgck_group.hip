@@ -35,10 +35,14 @@ constexpr int kGrpStage = 2048;
 // publishes after the stores' own completion instead of an L2 write-back.
 // LDSP: packet bytes in LDS (p.base and p.zero generic pointers into it).
 // FL: the flags, known at compile time (0: p.flags, read at run time).
+// IP6: the batch carries CGCK_IP6 (cksum6_kernel): the records are IPv6
+// headers, the L4 region is found by the extension-header walk (v6_walk) and
+// summed directly (eat6); launches only, never a burst-server body.
 template <int G, int S, int U, bool DESC, bool NT, bool LDSD = false, bool SYS = false, bool SYSST = false,
-	  bool LDSP = false, uint32_t FL = 0>
+	  bool LDSP = false, uint32_t FL = 0, bool IP6 = false>
 __device__ __forceinline__ void cksum_body(const KParams &p, uint32_t bid, uint32_t nb)
 {
+	static_assert(!IP6 || (!LDSD && !SYS && !LDSP && FL == 0), "IPv6 batches take the launch path");
 	__shared__ uint32_t so[kGrpStage];
 	constexpr int GPB = 256 / G;        // groups per block
 	constexpr int PPB = GPB * U;        // packets per block iteration
@@ -68,6 +72,7 @@ __device__ __forceinline__ void cksum_body(const KParams &p, uint32_t bid, uint3
 		uint32_t b0[U], proto[U], tl[U]; // tl: ntohs(ip_len)'s bytes (kFlagRx)
 		uint4 v[U][S];
 		int nch[U];
+		uint32_t nh0[U]; // IP6: header byte 6
 #pragma unroll
 		for (int u = 0; u < U; ++u) {
 			if constexpr (LDSD)
@@ -84,6 +89,11 @@ __device__ __forceinline__ void cksum_body(const KParams &p, uint32_t bid, uint3
 			b0[u] = 0;
 			proto[u] = 0;
 			tl[u] = 0;
+			nh0[u] = 0;
+			if constexpr (IP6) {
+				if (need_hdr && (flags & CGCK_L4) && pk[u].ok && span >= 40)
+					nh0[u] = *gbl_at<const uint8_t>(a0 + 6);
+			} else
 			if (!SYS && need_hdr && pk[u].ok && span > 0) {
 				b0[u] = ld8q<LDSP>(a0);
 				if (span > 9)
@@ -136,8 +146,19 @@ __device__ __forceinline__ void cksum_body(const KParams &p, uint32_t bid, uint3
 			if (rx)
 				rxm = rx_meta(pk[u].len, b0[u], tl[u] >> 8, tl[u] & 0xffu, proto[u], &cover);
 			const int len = (int)cover;
+			// IP6: the walk's dependent byte loads (only a packet with
+			// extension headers has any) come after the chunk loads' issue
+			V6 v6 = {40, 0, kV6Ok};
+			if constexpr (IP6) {
+				if (need_hdr && (flags & CGCK_L4))
+					v6 = v6_walk(pk[u].a0, len, nh0[u]);
+				else if (len < 40)
+					v6.st = kV6BadLen;
+			}
+			const int l4 = v6.st == kV6Ok ? v6.l4_off : len; // IP6: the region summed is [l4, len)
+			const int fa = IP6 && v6.st == kV6Ok && v6_field(v6.nh) >= 0 ? v6.l4_off + v6_field(v6.nh) : -1;
 			const int hl = (int)(b0[u] & 15) * 4;
-			const int fo = (need_hdr && (flags & (CGCK_L4)) && len >= 20 && len >= hl &&
+			const int fo = (!IP6 && need_hdr && (flags & (CGCK_L4)) && len >= 20 && len >= hl &&
 					l4_field(proto[u], flags) >= 0 &&
 					hl + l4_field(proto[u], flags) + 2 <= len)
 					       ? l4_field(proto[u], flags)
@@ -146,6 +167,12 @@ __device__ __forceinline__ void cksum_body(const KParams &p, uint32_t bid, uint3
 #pragma unroll
 			for (int s = 0; s < S; ++s) {
 				const int k = s * G + gl;
+				if (IP6 && need_hdr) {
+					if (s * G * 16 < 96)
+						eat6<true>(pt, v[u][s], k, q, len, l4, fa, flags);
+					else
+						eat6<false>(pt, v[u][s], k, q, len, l4, fa, flags);
+				} else
 				if (need_hdr && s * G * 16 < 96)
 					eat<true>(pt, v[u][s], k, q, len, hl, fo, flags);
 				else
@@ -157,6 +184,12 @@ __device__ __forceinline__ void cksum_body(const KParams &p, uint32_t bid, uint3
 			for (int s = S; __any(s * G < nch[u]); ++s) {
 				const int k = s * G + gl;
 				uint4 w = k < nch[u] ? ldq<NT, LDSP>(c0 + k) : make_uint4(0, 0, 0, 0);
+				if (IP6 && need_hdr) {
+					if (s * G * 16 < 96)
+						eat6<true>(pt, w, k, q, len, l4, fa, flags);
+					else
+						eat6<false>(pt, w, k, q, len, l4, fa, flags);
+				} else
 				if (need_hdr && s * G * 16 < 96)
 					eat<true>(pt, w, k, q, len, hl, fo, flags);
 				else
@@ -169,7 +202,8 @@ __device__ __forceinline__ void cksum_body(const KParams &p, uint32_t bid, uint3
 			if (need_hdr) {
 				ip = gsum<(G < 8 ? G : 8)>(pt.ip);
 				ps = gsum<(G < 8 ? G : 8)>(pt.ps);
-				fld = gsum<(G < 8 ? G : 8)>(pt.fld);
+				// (IP6: the field may lie in any chunk of the packet)
+				fld = IP6 ? gsum<G>(pt.fld) : gsum<(G < 8 ? G : 8)>(pt.fld);
 			}
 			if (gl != 0 || !pk[u].ok)
 				continue; // lane 0 of the group finishes the packet
@@ -180,6 +214,29 @@ __device__ __forceinline__ void cksum_body(const KParams &p, uint32_t bid, uint3
 			if (raw) {
 				uint32_t f = fold16(tot);
 				lo = finish(odd ? bswap16(f) : f);
+			} else if (IP6) {
+				// lo stays 0 (no header checksum), BAD_IP is never set and
+				// nothing is stored at +10
+				const bool l4ok = (flags & CGCK_L4) && v6.st == kV6Ok;
+				if (v6.st == kV6BadLen) {
+					verdict = CGCK_BAD_LEN;
+				} else if (l4ok) {
+					// pseudo-header: src, dst, the upper-layer length as 32
+					// bits big-endian (below 65536: one nonzero word), three
+					// zero bytes and nh
+					uint32_t f = fold16(fold16(tot) + fold16(ps));
+					f = odd ? bswap16(f) : f;
+					f += (v6.nh << 8) + bswap16((uint32_t)(len - l4) & 0xffffu);
+					hi = finish(fold16(f));
+					uint32_t sl4 = fld >> 16;
+					if (odd)
+						sl4 = bswap16(sl4);
+					if ((flags & CGCK_VERIFY) && fa >= 0 &&
+					    !((flags & CGCK_V_UDP_ZERO_SKIP) && v6.nh == 17 && sl4 == 0) && hi != sl4)
+						verdict |= CGCK_BAD_L4;
+					if ((flags & CGCK_STORE) && fa >= 0)
+						store16p<SYSST>(reinterpret_cast<uint8_t *>(pk[u].a0) + fa, hi);
+				}
 			} else if (!(flags & kFlagNoLenCheck) && (len < 20 || len < hl)) {
 				verdict = CGCK_BAD_LEN;
 			} else {
@@ -250,6 +307,14 @@ template <int G, int S, int U, bool DESC, bool NT>
 __global__ __launch_bounds__(256) void cksum_kernel(KParams p)
 {
 	cksum_body<G, S, U, DESC, NT>(p, blockIdx.x, gridDim.x);
+}
+
+// The same shapes over IPv6 records (CGCK_IP6), a kernel of its own so the
+// IPv4 kernels keep their code and their names.
+template <int G, int S, int U, bool DESC, bool NT>
+__global__ __launch_bounds__(256) void cksum6_kernel(KParams p)
+{
+	cksum_body<G, S, U, DESC, NT, false, false, false, false, 0, true>(p, blockIdx.x, gridDim.x);
 }
 
 // --------------------------------------------------------------------------
@@ -871,6 +936,16 @@ static hipError_t launch_t(const KParams &p, int max_blocks, bool nt, hipStream_
 	int blocks = (int)(want < (uint64_t)max_blocks ? want : (uint64_t)max_blocks);
 	if (blocks < 1)
 		blocks = 1;
+	if (p.flags & CGCK_IP6) {
+		if (nt) {
+			CGCK_NOTE_KERNEL("cksum6_kernel<%d, %d, %d, %s, true>", G, S, U, tf(DESC));
+			hipLaunchKernelGGL((cksum6_kernel<G, S, U, DESC, true>), dim3(blocks), dim3(256), 0, st, p);
+		} else {
+			CGCK_NOTE_KERNEL("cksum6_kernel<%d, %d, %d, %s, false>", G, S, U, tf(DESC));
+			hipLaunchKernelGGL((cksum6_kernel<G, S, U, DESC, false>), dim3(blocks), dim3(256), 0, st, p);
+		}
+		return hipGetLastError();
+	}
 	if (nt) {
 		CGCK_NOTE_KERNEL("cksum_kernel<%d, %d, %d, %s, true>", G, S, U, tf(DESC));
 		hipLaunchKernelGGL((cksum_kernel<G, S, U, DESC, true>), dim3(blocks), dim3(256), 0, st, p);

@@ -254,6 +254,8 @@ constexpr const char *tf(bool b) { return b ? "true" : "false"; }
 hipError_t launch_synth_fill(uint8_t *base, uint64_t nbytes, uint64_t seed, int num_cus, hipStream_t st);
 hipError_t launch_synth_stamp(uint8_t *base, uint64_t n, uint64_t stride, uint32_t len, int num_cus,
 			      hipStream_t st);
+hipError_t launch_synth_stamp6(uint8_t *base, uint64_t n, uint64_t stride, uint32_t len, uint32_t nh, int num_cus,
+			       hipStream_t st);
 hipError_t launch_probe_read(const void *src, uint64_t bytes, uint32_t *sink, int num_cus, int variant,
 			     hipStream_t st);
 hipError_t launch_synth_imix(uint8_t *base, uint32_t *desc, uint64_t n, int num_cus, hipStream_t st);

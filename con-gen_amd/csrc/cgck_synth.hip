@@ -60,6 +60,39 @@ __global__ __launch_bounds__(256) void synth_stamp_strided_kernel(uint8_t *base,
 		stamp(base + k * stride, len);
 }
 
+// IPv6 stamp (cgck_synth_strided_ip6): version word, payload length, next
+// header, and the checksum field of nh zeroed when the packet holds it.
+__global__ __launch_bounds__(256) void synth_stamp6_strided_kernel(uint8_t *base, uint64_t n, uint64_t stride,
+								   uint32_t len, uint32_t nh)
+{
+	const int fo = v6_field(nh);
+	for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (uint64_t)gridDim.x * 256) {
+		uint8_t *ip = base + k * stride;
+		ip[0] = 0x60;
+		ip[1] = 0;
+		ip[2] = 0;
+		ip[3] = 0;
+		ip[4] = (uint8_t)((len - 40) >> 8);
+		ip[5] = (uint8_t)(len - 40);
+		ip[6] = (uint8_t)nh;
+		if (fo >= 0 && 40 + fo + 2 <= (int)len) {
+			ip[40 + fo] = 0;
+			ip[40 + fo + 1] = 0;
+		}
+	}
+}
+
+hipError_t launch_synth_stamp6(uint8_t *base, uint64_t n, uint64_t stride, uint32_t len, uint32_t nh, int num_cus,
+			       hipStream_t st)
+{
+	uint64_t want = (n + 255) / 256;
+	int blocks = (int)(want < (uint64_t)num_cus * 8 ? want : (uint64_t)num_cus * 8);
+	if (blocks < 1)
+		blocks = 1;
+	hipLaunchKernelGGL(synth_stamp6_strided_kernel, dim3(blocks), dim3(256), 0, st, base, n, stride, len, nh);
+	return hipGetLastError();
+}
+
 __constant__ uint16_t c_imix_len[12] = {64, 576, 64, 64, 576, 64, 1500, 64, 576, 64, 64, 576};
 __constant__ uint16_t c_imix_off[12] = {0, 64, 640, 704, 768, 1344, 1408, 2908, 2972, 3548, 3612, 3676};
 

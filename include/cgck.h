@@ -85,7 +85,41 @@ enum {
 	CGCK_VERIFY      = 1u << 6, /* compare with the stored fields (implies ZERO_FIELDS), verdict bits */
 	CGCK_V_IP_ZERO_IS_FFFF = 1u << 7, /* bsd44 ip_input.c:46-48: a received ip_sum of 0 counts as 0xFFFF */
 	CGCK_V_UDP_ZERO_SKIP   = 1u << 8, /* udp_usrreq.c:86: uh_sum == 0 means "not checksummed" */
+	CGCK_IP6         = 1u << 9, /* the record at l3_off is an IPv6 header (40 bytes); see below */
 };
+/* CGCK_IP6.  ip_len (descriptor or strided argument) is the bytes covered from
+ * the first header byte, 40 + payload, at most 65535 (no jumbograms); the
+ * header's own payload-length field is not consulted.  The other flags keep
+ * their meaning:
+ *   CGCK_RAW   unchanged (in_cksum of the whole region).
+ *   CGCK_IP    accepted and inert: IPv6 has no header checksum, so out.lo = 0,
+ *              CGCK_BAD_IP is never set and nothing is stored at +10
+ *              (CGCK_V_IP_ZERO_IS_FFFF is inert too).  The GEN_BOTH / FILL_BOTH
+ *              / VERIFY_* sets therefore work with `| CGCK_IP6`.
+ *   CGCK_L4    out.hi = the upper-layer checksum.  The L4 header is found from
+ *              l4_off = 40, nh = byte 6: Hop-by-Hop (0), Routing (43) and
+ *              Destination Options (60) advance by (b[1] + 1) * 8, AH (51) by
+ *              (b[1] + 2) * 4, at most 8 extension headers.  A Fragment header
+ *              (44) means the packet has no L4 result: out.hi = 0, nothing
+ *              stored or compared, no bad bit.  Any other value is the
+ *              terminal nh.  The sum covers the ip_len - l4_off bytes at l4_off
+ *              plus the 40-byte pseudo-header {src, dst (header bytes 8..39),
+ *              the upper-layer length as 32 bits big-endian, three zero bytes,
+ *              nh} (RFC 8200 §8.1).  Checksum fields: TCP (6) +16, UDP (17) +6,
+ *              ICMPv6 (58) +2 after l4_off; any other terminal nh (59 and
+ *              unknown ones included) has no field: its sum is still returned
+ *              in out.hi, nothing is zeroed, stored or compared.
+ *   CGCK_ZERO_FIELDS, CGCK_STORE, CGCK_VERIFY, CGCK_V_UDP_ZERO_SKIP
+ *              as for IPv4, on the field found above (V_UDP_ZERO_SKIP is
+ *              honoured as given: an IPv6 caller leaves it out, RFC 8200 §8.1).
+ *   CGCK_L4_NOPSEUDO | CGCK_IP6 is -EINVAL.
+ * CGCK_BAD_LEN: ip_len < 40, or, with CGCK_L4, an extension header (its first
+ * two bytes), the start of the L4 region or the checksum field the chain names
+ * lies past ip_len, or there is a ninth extension header; out = 0, nothing
+ * stored, not counted as bad.
+ * Accepted by cgck_strided, cgck_desc and cgck_desc_host (with a burst server
+ * open such a batch takes the launch path); cgck_burst_request refuses it with
+ * -EINVAL.  The RX / TX windows and the drop-in symbols remain IPv4. */
 #define CGCK_GEN_BOTH    (CGCK_IP | CGCK_L4)
 #define CGCK_FILL_BOTH   (CGCK_IP | CGCK_L4 | CGCK_ZERO_FIELDS | CGCK_STORE)
 #define CGCK_VERIFY_BSD  (CGCK_IP | CGCK_L4 | CGCK_VERIFY | CGCK_V_IP_ZERO_IS_FFFF | CGCK_V_UDP_ZERO_SKIP)
@@ -97,7 +131,8 @@ enum {
 	CGCK_BAD_L4  = 1u << 1, /* -> tcps_rcvbadsum / udps_badsum (netstat.h:103,129) */
 	CGCK_BAD_LEN = 1u << 2, /* header modes only: ip_len < 20 or ip_len < ip_hl*4
 	                           (ip_input.c:24-37 drops these before any checksum):
-	                           out = 0, nothing stored, not counted as bad */
+	                           out = 0, nothing stored, not counted as bad
+	                           (CGCK_IP6: see that flag) */
 };
 
 /* Error codes are negative errno values; this gives a thread-local message. */
@@ -364,6 +399,12 @@ int cgck_burst_request(cgck_ctx_t *ctx, const void *dev_base, uint64_t range,
  * densely, with the descriptors written to `desc`. */
 int cgck_synth_strided(cgck_ctx_t *ctx, void *base, uint64_t n, uint64_t stride,
 		       uint32_t ip_len, uint64_t seed, void *stream);
+/* The same byte stream stamped as IPv6 packets (40 <= ip_len <= stride,
+ * ip_len <= 65535): bytes 0-3 = 60 00 00 00, bytes 4-5 = ip_len - 40
+ * big-endian, byte 6 = nh, and the checksum field of nh (TCP +16, UDP +6,
+ * ICMPv6 +2 after the 40-byte header) zeroed when the packet holds it. */
+int cgck_synth_strided_ip6(cgck_ctx_t *ctx, void *base, uint64_t n, uint64_t stride,
+			   uint32_t ip_len, uint32_t nh, uint64_t seed, void *stream);
 int cgck_synth_imix(cgck_ctx_t *ctx, void *base, cgck_desc_t *desc, uint64_t n,
 		    uint64_t seed, void *stream);
 uint64_t cgck_imix_bytes(uint64_t n); /* bytes an n-packet IMIX batch occupies */
