@@ -33,6 +33,14 @@
 //    words are broadcast reads; every lane computes the frame's result (the
 //    cost is per wave either way) and lane 0 of the group stages it.
 //
+//  * A step's geometry is the same for every step (base, stride multiples of
+//    4 and steps of 4 frames: the step's start keeps base & 15), so the
+//    lanes' slot offsets and selects are computed once per wave, and while
+//    the step to issue is full (four live frames) its six DMAs are one asm
+//    statement off a scalar cursor, in a loop of its own per number of whole
+//    KiBs; the general issue() serves a wave's last steps
+//    (cgck_dense_kernel.inc, profiles/dstr_geom/).
+//
 // Scope (dstr_ok): strided batches, base / stride / l3_off multiples of 4,
 // 20 <= ip_len <= 1520, stride <= 1520, flags RAW or any of IP / L4 /
 // L4_NOPSEUDO (no field zeroing, verify or in-place store), an output array

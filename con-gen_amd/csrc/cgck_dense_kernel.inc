@@ -15,6 +15,55 @@ constexpr int kDsChunks = kDsS * 64;        // 16-byte chunks per slot
 // reads in one process, twice, bit-exact; profiles/r04/dstr_ab/.)
 static_assert(((15 + 3 * 1520) >> 4) + 16 * (kDsS - 1) + 15 < kDsChunks, "a reducing lane's chunk lies in its slot");
 
+// The six DMAs of a full step (four live frames) in ONE statement: M0 is
+// saved and restored once and advanced by 1 KiB between the DMAs (the
+// instruction's offset field is not used: what it does to the LDS side is
+// not relied on), each write of M0 followed by its s_nop 0.  The step's
+// aligned start `a` is wave-uniform (an SGPR pair), and of the step's span
+// NW KiBs are whole for every lane: those take `a` as the scalar base and the
+// lane's constant offset off[i] = 1024 i + 16 lane.  KiB NW is partial: `pa`
+// is the lane's address, or the zero line past the step's last chunk.  The
+// KiBs after it lie past the step and read the zero line (`z`, offset vz = 0).
+// Always six DMAs, so the counted waits keep their meaning.  The opening
+// s_nop 2 puts five wait states between whatever wrote `a` and the first DMA
+// that reads it as its base.
+#define CGCK_DS_OPEN "s_mov_b32 %[k], m0\n\ts_mov_b32 m0, %[slot]\n\ts_nop 2\n\t"
+#define CGCK_DS_NEXT "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
+#define CGCK_DS_W(i) "global_load_lds_dwordx4 %[o" #i "], %[a] nt\n\t" CGCK_DS_NEXT
+#define CGCK_DS_P "global_load_lds_dwordx4 %[pa], off nt\n\t"
+#define CGCK_DS_Z CGCK_DS_NEXT "global_load_lds_dwordx4 %[vz], %[z] nt\n\t"
+#define CGCK_DS_ASM(body)                                                                               \
+	asm volatile(CGCK_DS_OPEN body "s_mov_b32 m0, %[k]"                                              \
+		     : [k] "=&s"(keep)                                                                   \
+		     : [slot] "s"(slot), [a] "s"(a), [o0] "v"(off[0]), [o1] "v"(off[1]), [o2] "v"(off[2]), \
+		       [o3] "v"(off[3]), [o4] "v"(off[4]), [pa] "v"(pa), [vz] "v"(vz), [z] "s"(z)        \
+		     : "memory", "scc")
+template <int NW>
+__device__ __forceinline__ void dstr_issue_full(uint64_t a, uint32_t slot, const uint32_t (&off)[kDsS - 1], const void *pa,
+						 const void *z, uint32_t vz)
+{
+	static_assert(NW >= 0 && NW < kDsS, "a step of four frames (<= 6091 bytes) has at most five whole KiBs");
+	uint32_t keep;
+	if constexpr (NW == 5)
+		CGCK_DS_ASM(CGCK_DS_W(0) CGCK_DS_W(1) CGCK_DS_W(2) CGCK_DS_W(3) CGCK_DS_W(4) CGCK_DS_P);
+	else if constexpr (NW == 4)
+		CGCK_DS_ASM(CGCK_DS_W(0) CGCK_DS_W(1) CGCK_DS_W(2) CGCK_DS_W(3) CGCK_DS_P CGCK_DS_Z);
+	else if constexpr (NW == 3)
+		CGCK_DS_ASM(CGCK_DS_W(0) CGCK_DS_W(1) CGCK_DS_W(2) CGCK_DS_P CGCK_DS_Z CGCK_DS_Z);
+	else if constexpr (NW == 2)
+		CGCK_DS_ASM(CGCK_DS_W(0) CGCK_DS_W(1) CGCK_DS_P CGCK_DS_Z CGCK_DS_Z CGCK_DS_Z);
+	else if constexpr (NW == 1)
+		CGCK_DS_ASM(CGCK_DS_W(0) CGCK_DS_P CGCK_DS_Z CGCK_DS_Z CGCK_DS_Z CGCK_DS_Z);
+	else
+		CGCK_DS_ASM(CGCK_DS_P CGCK_DS_Z CGCK_DS_Z CGCK_DS_Z CGCK_DS_Z CGCK_DS_Z);
+}
+#undef CGCK_DS_ASM
+#undef CGCK_DS_Z
+#undef CGCK_DS_P
+#undef CGCK_DS_W
+#undef CGCK_DS_NEXT
+#undef CGCK_DS_OPEN
+
 // IP6 (dstr6_kernel, CGCK_IP6): the same stream; the reducing wave stages
 // the frame's sum, the sum of its first 8 bytes and byte 6, and the writer
 // wave finishes with the no-extension identity (v6_dense, cgck_device.h): a
@@ -46,7 +95,11 @@ __global__ __launch_bounds__(128) void CGCK_DSTR_KERNEL(KParams p)
 	if (b >= NC)
 		return;
 	const uint32_t nsteps = (uint32_t)((NC - b + G - 1) / G * C);
-	const uint32_t mode = p.contig; // lab A/B modes (launch_dstr); 0 in the product
+#if CGCK_LAB
+	const uint32_t mode = p.contig; // lab A/B modes (launch_dstr)
+#else
+	constexpr uint32_t mode = 0; // (the product launcher sets none: no test of it per step)
+#endif
 	auto cfirst = [&](uint32_t k) { return (b + (uint64_t)k * G) * SC; }; // chunk k's first frame
 
 	// a frame's result from its folded sums (tot over the frame, ip over the
@@ -228,10 +281,77 @@ __global__ __launch_bounds__(128) void CGCK_DSTR_KERNEL(KParams p)
 				glds16_nt(live && src <= e ? reinterpret_cast<const void *>(src) : zero, slot + 1024 * i);
 		}
 	};
+	// The geometry of a step is the same for every step of every wave.
+	// dstr_ok: base + l3_off and stride are multiples of 4.  Chunks start at
+	// multiples of SC, steps at multiples of 4 inside them, so a step's first
+	// frame f0 is a multiple of 4 and f0 * stride one of 16.  Hence
+	// (base + f0 * stride) & 15 == base & 15 =: al, the step's aligned start
+	// is a = base + f0 * stride - al, and frame g of the step lies al + g *
+	// stride bytes into the slot whatever the step.  Everything a lane derives
+	// from that (its chunk offsets in the slot, which dwords of its first and
+	// last chunk lie outside the frame, which of its six chunks lie inside) is
+	// computed here once, not per step, and the selects become multipliers of
+	// the v_dot2 sums (hsum_sel) or masks: no multiply and no compare on them
+	// remains in the loop.  (opaque: each value in a register of its own,
+	// not re-derived in the loop.)
+	static_assert(SC % 4 == 0, "a step's first frame is a multiple of 4");
+	static_assert(D < C, "the prologue's steps lie in the first chunk");
+	const int al = (int)(base & 15);
+	const int o = al + g * (int)stride; // frame g's byte offset in the slot
+	const int q = o & 15, c0 = o >> 4;
+	const int nch = (q + len + 15) >> 4;
+	const int e = q + len - 16 * (nch - 1); // bytes of the last chunk in the frame
+	const uint32_t rd_w = opaque(16u * (uint32_t)(c0 + gl));      // the lane's chunks: + 256 s
+	[[maybe_unused]] const uint32_t rd_t = opaque(16u * (uint32_t)(c0 + nch - 1)); // the frame's last chunk
+	[[maybe_unused]] const uint32_t rd_h = opaque((uint32_t)o);                    // the header
+	uint32_t bmul[kDsS]; // chunk s of the lane lies in the frame
+#pragma unroll
+	for (int s = 0; s < kDsS; ++s)
+		bmul[s] = opaque(16 * s + gl < nch ? kHsumAll : 0u);
+	// group lane 0: the q bytes (whole dwords) of the first chunk before the
+	// frame, and the bytes of the last chunk after it (whole dwords when len is
+	// a multiple of 4, else byte masks)
+	const uint32_t lm1 = opaque(gl == 0 && q >= 4 ? kHsumAll : 0u), lm2 = opaque(gl == 0 && q >= 8 ? kHsumAll : 0u),
+		       lm3 = opaque(gl == 0 && q >= 12 ? kHsumAll : 0u);
+#if CGCK_DSTR_REGHDR
+	const bool tl = true; // (the lane holding the last chunk, chosen per step)
+#else
+	const bool tl = gl == 0;
+#endif
+	const uint32_t tm0 = opaque(tl ? dmask(0, 0, e, 16) : 0u), tm1 = opaque(tl ? dmask(0, 1, e, 16) : 0u),
+		       tm2 = opaque(tl ? dmask(0, 2, e, 16) : 0u), tm3 = opaque(tl ? dmask(0, 3, e, 16) : 0u);
+
+	// A full step (four live frames) spans span + 16 bytes from its aligned
+	// start, the same for every full step: nw of its KiBs are whole, KiB nw is
+	// partial (lanes past the span read the zero line), the rest read the zero
+	// line.  The first jfull steps of the wave are full: all of them, unless
+	// its last chunk is the batch's last, partial one.
+	const uint32_t span = ((uint32_t)al + 3 * (uint32_t)stride + (uint32_t)len - 1) & ~15u;
+	const uint32_t nw = (span + 16) >> 10; // KiBs i with 1024 i + 1008 <= span: at most 5
+	uint32_t off[kDsS - 1];
+#pragma unroll
+	for (int i = 0; i < kDsS - 1; ++i)
+		off[i] = opaque(1024u * i + 16u * lane);
+	const uint32_t poff = 1024 * nw + 16 * lane;
+	const uint32_t pmask = opaque(poff <= span ? ~0u : 0u);
+	const uint32_t vz = opaque(0u);
+	const uint32_t klast = nsteps / C - 1;
+	const uint64_t lrem = (n - cfirst(klast)) / 4;
+	const uint32_t jfull = klast * C + (lrem < (uint64_t)C ? (uint32_t)lrem : (uint32_t)C);
+	// the aligned start of the step to issue next (j + D), advanced by four
+	// frames inside a chunk and by the jump to the wave's next chunk at its end
+	const uint64_t step4 = 4 * stride, cjump = (G * SC - 4 * (C - 1)) * stride;
+	uint64_t ia = base - (uint64_t)al + (cfirst(0) + 4 * D) * stride;
+	uint32_t slot_off = 0; // (j % D) * kDsSlot
+
 #pragma unroll
 	for (int d = 0; d < D; ++d)
 		issue(d);
-	for (uint32_t j = 0; j < nsteps; ++j) {
+	// One step.  NW >= 0: step j + D is full and has NW whole KiBs (the first
+	// loop below); NW < 0: the general issue() (the wave's last steps, and the
+	// refills past them).
+	auto step = [&](uint32_t j, auto nwc) __attribute__((always_inline)) {
+		constexpr int NW = decltype(nwc)::value;
 		// Wait for step j's DMA.  Issued after it: the D - 1 later steps' DMA
 		// and (without the writer wave) the last chunk flush's store when it
 		// came after step j's DMA.
@@ -245,27 +365,35 @@ __global__ __launch_bounds__(128) void CGCK_DSTR_KERNEL(KParams p)
 		if (!W || mode == 6)
 			wg_barrier();
 		uint32_t *sc = so + (W ? ((j / C) & 1) * 8 * C : 0); // this chunk's staging
+		auto refill = [&]() __attribute__((always_inline)) { // step j + D into the slot of step j
+			if constexpr (NW >= 0) {
+				const uint32_t slot = lds0 + slot_off;
+				const uint64_t pl = ia + poff;
+				const uint64_t zl = reinterpret_cast<uint64_t>(zero);
+				const void *pa = reinterpret_cast<const void *>(
+					(uint64_t)pick(pmask, (uint32_t)pl, (uint32_t)zl) |
+					(uint64_t)pick(pmask, (uint32_t)(pl >> 32), (uint32_t)(zl >> 32)) << 32);
+				dstr_issue_full<NW>(ia, slot, off, pa, zero, vz);
+				ia += ((j + D + 1) % C) == 0 ? cjump : step4;
+			} else {
+				issue(j + D);
+			}
+		};
 		if (mode == 3) { // lab: the DMA pipeline alone
-			issue(j + D);
+			refill();
 		} else {
-			const uint64_t f0 = sfirst(j);
-			const uint64_t a = (base + f0 * stride) & ~(uint64_t)15;
-			const int o = (int)(base + (f0 + g) * stride - a); // frame g's byte offset in the slot
-			const int q = o & 15, c0 = o >> 4;
-			const int nch = (q + len + 15) >> 4;
-			const uint8_t *sl = smem + (j % D) * kDsSlot;
+			const uint8_t *sl = smem + slot_off;
 			uint4 w[kDsS];
 #pragma unroll
-			for (int s = 0; s < kDsS; ++s) {
-				const int c = c0 + 16 * s + gl;
-				w[s] = *reinterpret_cast<const uint4 *>(sl + 16 * c);
-			}
+			for (int s = 0; s < kDsS; ++s)
+				w[s] = *reinterpret_cast<const uint4 *>(sl + rd_w + 256 * s);
 #if CGCK_DSTR_REGHDR
 			// (lab A/B) only the six chunk reads before the refill: the last
 			// chunk is the register of the lane holding it, the header dwords
 			// come from w[0] of this lane and the next (DPP row_shl:1)
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-			issue(j + D);
+			refill();
+			const uint64_t f0 = sfirst(j);
 			uint4 wt = make_uint4(0, 0, 0, 0);
 			bool ht = false;
 #pragma unroll
@@ -298,8 +426,8 @@ __global__ __launch_bounds__(128) void CGCK_DSTR_KERNEL(KParams p)
 					ip = hsum(*gbl_at<const uint32_t>(fa + 4 * i), ip);
 			}
 #else
-			const uint4 wt = *reinterpret_cast<const uint4 *>(sl + 16 * (c0 + nch - 1)); // the last chunk
-			const uint32_t *hw = reinterpret_cast<const uint32_t *>(sl + o);
+			const uint4 wt = *reinterpret_cast<const uint4 *>(sl + rd_t); // the last chunk
+			const uint32_t *hw = reinterpret_cast<const uint32_t *>(sl + rd_h);
 			const uint32_t h0 = hw[0], h1 = hw[1], h2 = hw[2], h3 = hw[3], h4 = hw[4];
 			const uint32_t hd = h0 & 15;
 			// (IP6: the sum of the first 8 bytes, which the L4 sum leaves out)
@@ -312,38 +440,30 @@ __global__ __launch_bounds__(128) void CGCK_DSTR_KERNEL(KParams p)
 			// The slot's bytes are in registers: refill it now, so D steps stay
 			// in flight while this one is reduced.
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-			issue(j + D);
+			refill();
 #endif
 
-			// independent per-chunk chains (no dependent v_dot2 wait states),
-			// then the chunks inside the frame
+			// independent per-chunk chains (no dependent v_dot2 wait states);
+			// a chunk past the frame counts 0 by its multiplier
 			uint32_t cs[kDsS];
 #pragma unroll
 			for (int s = 0; s < kDsS; ++s)
-				cs[s] = sum4(w[s], 0);
+				cs[s] = sum4_sel(w[s], bmul[s], 0);
 			uint32_t body = 0;
 #pragma unroll
 			for (int s = 0; s < kDsS; ++s)
-				body += (len >= 1280 && s < 5) || 16 * s + gl < nch ? cs[s] : 0u;
-			// group lane 0: the q bytes (whole dwords) of the first chunk before
-			// the frame and the bytes of the last chunk after it
-			uint32_t lead = hsum(q >= 4 ? w[0].x : 0u, 0);
-			lead = hsum(q >= 8 ? w[0].y : 0u, lead);
-			lead = hsum(q >= 12 ? w[0].z : 0u, lead);
-			const int e = q + len - 16 * (nch - 1); // bytes of the last chunk in the frame
-			uint32_t tail;
-			if ((len & 3) == 0) { // whole dwords (kernel-uniform)
-				tail = hsum(e <= 4 ? wt.y : 0u, 0);
-				tail = hsum(e <= 8 ? wt.z : 0u, tail);
-				tail = hsum(e <= 12 ? wt.w : 0u, tail);
-			} else {
-				tail = msum(wt, 0, e, 16, 0);
-			}
+				body += cs[s];
+			// group lane 0 (the multipliers and masks are 0 in the other lanes):
+			// the bytes of the first chunk before the frame and of the last
+			// chunk after it
+			const uint32_t lead = hsum_sel(w[0].z, lm3, hsum_sel(w[0].y, lm2, hsum_sel(w[0].x, lm1, 0)));
 #if CGCK_DSTR_REGHDR
-			const uint32_t corr = (gl == 0 ? lead : 0u) + (ht ? tail : 0u);
+			const uint32_t tsel = ht ? ~0u : 0u;
 #else
-			const uint32_t corr = gl == 0 ? lead + tail : 0u;
+			constexpr uint32_t tsel = ~0u;
 #endif
+			const uint32_t tail = hsum(wt.w & tm3 & tsel, hsum(wt.z & tm2 & tsel, hsum(wt.y & tm1 & tsel, hsum(wt.x & tm0 & tsel, 0))));
+			const uint32_t corr = lead + tail;
 			uint32_t tot = fold16(body) + (0xffffu - fold16(corr));
 			tot = fold16(gsum<16>(tot));
 
@@ -358,6 +478,7 @@ __global__ __launch_bounds__(128) void CGCK_DSTR_KERNEL(KParams p)
 				sc[4 * (j % C) + g] = fin(tot, fold16(ip), ps, hd, proto);
 			}
 		}
+		slot_off = slot_off + kDsSlot == D * kDsSlot ? 0 : slot_off + kDsSlot;
 		if ((j + 1) % C == 0) {
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the chunk's outputs are in LDS
 			if (W)
@@ -365,7 +486,26 @@ __global__ __launch_bounds__(128) void CGCK_DSTR_KERNEL(KParams p)
 			else if (mode != 2) // lab mode 2: no output flush
 				flush(j / C, sc);
 		}
+	};
+	// The steps whose refill (step j + D) is full, then the rest.  Loops of
+	// their own, so the first holds no general issue() (none of its 64-bit
+	// multiplies, compares and branches), and one per nw, which never changes
+	// during a launch, so it holds no test of nw either.
+	const uint32_t jhot = (jfull > (uint32_t)D ? jfull : (uint32_t)D) - D;
+	uint32_t j = 0;
+	auto hot = [&](auto nwc) __attribute__((always_inline)) {
+		for (; j < jhot; ++j)
+			step(j, nwc);
+	};
+	switch (nw) {
+	case 5: hot(std::integral_constant<int, 5>{}); break;
+	case 4: hot(std::integral_constant<int, 4>{}); break;
+	case 3: hot(std::integral_constant<int, 3>{}); break;
+	case 2: hot(std::integral_constant<int, 2>{}); break;
+	case 1: hot(std::integral_constant<int, 1>{}); break;
+	default: hot(std::integral_constant<int, 0>{}); break;
 	}
+	for (; j < nsteps; ++j)
+		step(j, std::integral_constant<int, -1>{});
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
-

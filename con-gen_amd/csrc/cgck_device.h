@@ -27,6 +27,21 @@ __device__ __forceinline__ uint32_t sum4(const uint4 &w, uint32_t acc)
 	return hsum(w.w, hsum(w.z, hsum(w.y, hsum(w.x, acc))));
 }
 
+// The same with a lane's own multiplier pair: kHsumAll counts the dword,
+// 0 drops it, so a select that never changes (dstr_kernel's per-lane
+// geometry) costs no instruction of its own.
+constexpr uint32_t kHsumAll = 0x00010001u;
+__device__ __forceinline__ uint32_t hsum_sel(uint32_t w, uint32_t mul, uint32_t acc)
+{
+	typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+	return __builtin_amdgcn_udot2(__builtin_bit_cast(us2, w), __builtin_bit_cast(us2, mul), acc, false);
+}
+
+__device__ __forceinline__ uint32_t sum4_sel(const uint4 &w, uint32_t mul, uint32_t acc)
+{
+	return hsum_sel(w.w, mul, hsum_sel(w.z, mul, hsum_sel(w.y, mul, hsum_sel(w.x, mul, acc))));
+}
+
 // Byte mask of bytes [s, e) of a dword, s, e already clamped to [0, 4].
 __device__ __forceinline__ uint32_t bmask(int s, int e)
 {
