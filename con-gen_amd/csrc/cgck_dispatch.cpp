@@ -5,8 +5,8 @@
 // group (>= 1 KiB typical length otherwise, drop-in and window calls),
 // lpd / lpa (aligned fixed-length 20..64-byte strided batches), lpp (small
 // unaligned or descriptor packets) and slot2 (mid-size / mixed lengths).  The
-// A/B-only variants measured against them (slot, lppp, the other lpp shapes,
-// the LDS-DMA stream kernels, the probe kernels) are compiled only into
+// A/B-only variants measured against them (slot, lppp, the other lpp shapes:
+// cgck_lane_lab.inc; the LDS-DMA stream kernels, the probe kernels) are compiled only into
 // libcgck_lab.so (-DCGCK_LAB, tools/Makefile) for tools/ab_inproc.py and
 // tools/sweep.py.
 #include <stdarg.h>

@@ -8,8 +8,8 @@ asserts, per kernel:
   * the steady state of the loop holding the counted waits: along every path
     from one counted wait to the next, exactly the DMA instructions the wait
     constants assume (dstr: kDsS = 6 per step, cgck_dense.hip:49,258-260;
-    lpd: 4 per step, cgck_lane.hip:374-408; lpw: kLpwDma + 1 = 9 per round,
-    cgck_lane.hip:1533-1535, or two rounds when the step's first window was
+    lpd: 4 per step, cgck_lane_kernels.inc:119-133; lpw: kLpwDma + 1 = 9 per
+    round, cgck_lane.hip:820-828, or two rounds when the step's first window was
     issued at the step's top), no other load, and the flush's stores as
     designed (lpd C / 4 = 8 per chunk, lpw one deferred store per lane);
   * the prologue: D (dstr 3, lpd 2) steps of DMA before the first wait.
