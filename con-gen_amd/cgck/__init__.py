@@ -73,6 +73,7 @@ EXPORTS = (
     "cgck_rx_pending", "cgck_rx_ready", "cgck_tx_pending", "cgck_tx_ready",
     "cgck_window_stats_n", "cgck_thread_bind", "cgck_thread_device",
     "cgck_test_burst_seq", "cgck_test_burst_stale", "cgck_synth_strided_ip6",
+    "cgck_synth_imix_ip6", "cgck_synth_imix_ring_ip6",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -130,6 +131,9 @@ def bind(path):
     L.cgck_synth_strided.argtypes = [_vp, _vp, _u64, _u64, _u32, _u64, _vp]
     if hasattr(L, "cgck_synth_strided_ip6"):   # IPv6 addition (an older build loads without it)
         L.cgck_synth_strided_ip6.argtypes = [_vp, _vp, _u64, _u64, _u32, _u32, _u64, _vp]
+    if hasattr(L, "cgck_synth_imix_ip6"):      # the IPv6 IMIX pair (an older build loads without it)
+        L.cgck_synth_imix_ip6.argtypes = [_vp, _vp, _vp, _u64, _u32, _u64, _vp]
+        L.cgck_synth_imix_ring_ip6.argtypes = [_vp, _vp, _vp, _u64, _u64, _u32, _u32, _u64, _vp]
     L.cgck_synth_imix.argtypes = [_vp, _vp, _vp, _u64, _u64, _vp]
     L.cgck_synth_imix_ring.argtypes = [_vp, _vp, _vp, _u64, _u64, _u32, _u64, _vp]
     L.cgck_imix_bytes.restype = _u64
@@ -518,6 +522,16 @@ class Engine:
         """IMIX frames in ring slots (cgck_synth_imix_ring): n * stride bytes at base."""
         _check(load().cgck_synth_imix_ring(self.ctx, base, desc, n, stride, l3_off, seed, stream),
                "cgck_synth_imix_ring")
+
+    def synth_imix_ip6(self, base, desc, n, nh, seed, stream=None):
+        """cgck_synth_imix_ip6: the synth_imix set stamped as IPv6 packets of next
+        header nh (its checksum field zeroed)."""
+        _check(load().cgck_synth_imix_ip6(self.ctx, base, desc, n, nh, seed, stream), "cgck_synth_imix_ip6")
+
+    def synth_imix_ring_ip6(self, base, desc, n, stride, l3_off, nh, seed, stream=None):
+        """cgck_synth_imix_ring_ip6: the synth_imix_ring frames stamped as IPv6."""
+        _check(load().cgck_synth_imix_ring_ip6(self.ctx, base, desc, n, stride, l3_off, nh, seed, stream),
+               "cgck_synth_imix_ring_ip6")
 
     def toeplitz(self, data, n, stride, cnt, key, out, mask=0xFFFFFFFF, key_size=None, stream=None):
         """cgck_toeplitz: device data/out, host key.  Asynchronous."""

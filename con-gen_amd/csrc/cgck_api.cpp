@@ -1945,6 +1945,40 @@ extern "C" int cgck_synth_imix_ring(cgck_ctx_t *c, void *base, cgck_desc_t *desc
 	return 0;
 }
 
+extern "C" int cgck_synth_imix_ip6(cgck_ctx_t *c, void *base, cgck_desc_t *desc, uint64_t n, uint32_t nh,
+				   uint64_t seed, void *stream)
+{
+	if (!c || (n && (!base || !desc)))
+		return set_err(-EINVAL, "cgck_synth_imix_ip6: bad arguments");
+	if (((uintptr_t)base & 15) || ((uintptr_t)desc & 3))
+		return set_err(-EINVAL, "cgck_synth_imix_ip6: misaligned buffers");
+	if (nh > 255)
+		return set_err(-EINVAL, "cgck_synth_imix_ip6: need nh <= 255");
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = pick(c, stream);
+	HIP_TRY(launch_synth_fill((uint8_t *)base, cgck_imix_bytes(n), seed, c->num_cus, st));
+	HIP_TRY(launch_synth_imix6((uint8_t *)base, (uint32_t *)desc, n, 0, 0, nh, c->num_cus, st));
+	return 0;
+}
+
+extern "C" int cgck_synth_imix_ring_ip6(cgck_ctx_t *c, void *base, cgck_desc_t *desc, uint64_t n, uint64_t stride,
+					uint32_t l3_off, uint32_t nh, uint64_t seed, void *stream)
+{
+	if (!c || (n && (!base || !desc)))
+		return set_err(-EINVAL, "cgck_synth_imix_ring_ip6: bad arguments");
+	if (((uintptr_t)base & 15) || ((uintptr_t)desc & 3))
+		return set_err(-EINVAL, "cgck_synth_imix_ring_ip6: misaligned buffers");
+	if (l3_off > 0xffff || stride < (uint64_t)l3_off + 1500)
+		return set_err(-EINVAL, "cgck_synth_imix_ring_ip6: a slot must hold l3_off + 1500 bytes");
+	if (nh > 255)
+		return set_err(-EINVAL, "cgck_synth_imix_ring_ip6: need nh <= 255");
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = pick(c, stream);
+	HIP_TRY(launch_synth_fill((uint8_t *)base, n * stride, seed, c->num_cus, st));
+	HIP_TRY(launch_synth_imix6((uint8_t *)base, (uint32_t *)desc, n, stride, l3_off, nh, c->num_cus, st));
+	return 0;
+}
+
 extern "C" int cgck_probe_read(cgck_ctx_t *c, const void *src, uint64_t bytes, uint32_t *sink, void *stream)
 {
 	if (!c || !src || !sink || ((uintptr_t)src & 15))

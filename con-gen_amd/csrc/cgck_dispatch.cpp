@@ -4,7 +4,8 @@
 // picks by itself: dstr (dense strided >= 1 KiB frames, the 1500 B config),
 // group (>= 1 KiB typical length otherwise, drop-in and window calls),
 // lpd / lpa (aligned fixed-length 20..64-byte strided batches), lpp (small
-// unaligned or descriptor packets) and slot2 (mid-size / mixed lengths).  The
+// unaligned or descriptor packets), slot2 and lpw (mid-size / mixed lengths;
+// lpw6 for IPv6).  The
 // A/B-only variants measured against them (slot, lppp, the other lpp shapes:
 // cgck_lane_lab.inc; the LDS-DMA stream kernels, the probe kernels) are compiled only into
 // libcgck_lab.so (-DCGCK_LAB, tools/Makefile) for tools/ab_inproc.py and
@@ -45,6 +46,8 @@ bool lpd_ok(const KParams &p);
 bool lane6_ok(const KParams &p);
 hipError_t launch_lpw(const KParams &p, int num_cus, hipStream_t st);
 bool lpw_ok(const KParams &p);
+hipError_t launch_lpw6(const KParams &p, int num_cus, hipStream_t st);
+bool lpw6_ok(const KParams &p);
 hipError_t launch_dstr(const KParams &p, int num_cus, hipStream_t st);
 bool dstr_ok(const KParams &p);
 #if CGCK_LAB
@@ -67,7 +70,8 @@ hipError_t launch_slotd(const KParams &p, int num_cus, hipStream_t st);
 //     the batch has no verdicts, counters or stores and stride <= 64), 15
 //     lane per packet over DMA'd windows of a packed step's span (lpw, the
 //     default for descriptor batches of mixed lengths below 1 KiB under
-//     cgck_set_desc_layout(PACKED)), 11 dense strided frames streamed through
+//     cgck_set_desc_layout(PACKED); lpw6_kernel, cgck_lpw6.hip, for a CGCK_IP6
+//     batch), 11 dense strided frames streamed through
 //     LDS by DMA, four per step, with a writer wave (dstr, cgck_dense.hip: the
 //     default for strided batches of >= 1 KiB frames it accepts, dstr_ok;
 //     $CGCK_STR_OLD in the lab build: the first stream kernel,
@@ -79,8 +83,9 @@ hipError_t launch_slotd(const KParams &p, int num_cus, hipStream_t st);
 //     choice; one whose preconditions a batch fails falls back to lpa, lpp or
 //     group;
 //   A CGCK_IP6 batch goes only to a family with an IPv6 variant: dstr (dstr6),
-//   lpd / lpa (lpd6, lpa6: IP / L4 flags only, lane6_ok) and group (cksum6, the
-//   full semantics); any other choice, automatic or pinned, falls back to group;
+//   lpd / lpa (lpd6, lpa6: IP / L4 flags only, lane6_ok), lpw (lpw6: everything
+//   but STORE and the bad counters, lpw6_ok) and group (cksum6, the full
+//   semantics); any other choice, automatic or pinned, falls back to group;
 //   kNT (bit 4) nontemporal loads, kContig (bit 5) contiguous block ranges,
 //   kExplicit (bit 6) take bits 4-5 as given instead of the measured defaults,
 //   kPacked (bit 7) the context's layout hint says packed (cgck_set_desc_layout).
@@ -117,7 +122,8 @@ hipError_t launch_cksum(const KParams &p0, uint32_t len_hint, int num_cus, int k
 			: len_hint <= kLppUpToLen ? 2 : stream ? 15 : 9;
 	if (variant >= 2 && !lane_ok)
 		variant = 1;
-	if (ip6 && variant != 10 && variant != 11 && variant != 13) // lpp, slot2, lpw (and the lab's) are IPv4 only
+	if (ip6 && variant != 10 && variant != 11 && variant != 13 &&
+	    !(variant == 15 && lpw6_ok(p))) // lpp, slot2 (and the lab's) are IPv4 only
 		variant = 1;
 	if (variant == 10 && !lpa_ok)
 		variant = ip6 ? 1 : 2;
@@ -153,7 +159,7 @@ hipError_t launch_cksum(const KParams &p0, uint32_t len_hint, int num_cus, int k
 	case 13:
 		return launch_lpd(p, num_cus, st);
 	case 15:
-		return launch_lpw(p, num_cus, st);
+		return ip6 ? launch_lpw6(p, num_cus, st) : launch_lpw(p, num_cus, st);
 	case 11:
 #if CGCK_LAB
 		if (CGCK_ENV("CGCK_STR_OLD") && stream_ok(p)) // the first stream kernel (cgck_stream.hip)

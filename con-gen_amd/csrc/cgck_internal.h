@@ -261,5 +261,7 @@ hipError_t launch_probe_read(const void *src, uint64_t bytes, uint32_t *sink, in
 hipError_t launch_synth_imix(uint8_t *base, uint32_t *desc, uint64_t n, int num_cus, hipStream_t st);
 hipError_t launch_synth_ring(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t stride, uint32_t l3_off, int num_cus,
 			     hipStream_t st);
+hipError_t launch_synth_imix6(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t stride, uint32_t l3_off,
+			      uint32_t nh, int num_cus, hipStream_t st);
 
 } // namespace cgck

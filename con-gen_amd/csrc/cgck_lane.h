@@ -255,6 +255,113 @@ __device__ __forceinline__ void finish(const KParams &p, uint64_t k, uint64_t a0
 }
 
 // --------------------------------------------------------------------------
+// IPv6 finish of a lane that holds its packet's whole sum (lpw6_kernel)
+// --------------------------------------------------------------------------
+//
+// The lane has T, the folded sum over [0, len) of its packet, and the header
+// chunks.  With no extension header the L4 sum is that of [8, len) plus the
+// pseudo-header's htons(len - 40) and nh << 8, so the header
+// gives three things: h8 = the sum of bytes [0, 8), nh = byte 6 and, for
+// ZERO_FIELDS / VERIFY, the stored checksum field of nh at 40 + {16, 6, 2}:
+// packet-relative dwords 14, 11 and 10, which with q <= 15 lie in chunks 0..4.
+
+struct Hdr6 {
+	uint32_t h8;  // folded sum over [0, 8), packet-relative
+	uint32_t nh;  // byte 6
+	uint32_t fl4; // the stored field at 40 + v6_field(nh) as a host u16 (ZERO_FIELDS / VERIFY, no extension header)
+};
+
+// v[0..5]: the packet's first chunks (those past its end hold anything).
+template <int NV>
+__device__ __forceinline__ Hdr6 header6(const uint4 (&v)[NV], int q, uint32_t flags, bool act)
+{
+	static_assert(NV >= 6, "dword 14 at q = 15 ends in chunk 4");
+	uint32_t D[24];
+#pragma unroll
+	for (int i = 0; i < 6; ++i) {
+		D[4 * i + 0] = v[i].x;
+		D[4 * i + 1] = v[i].y;
+		D[4 * i + 2] = v[i].z;
+		D[4 * i + 3] = v[i].w;
+	}
+	Align a;
+	const int qd = q >> 2;
+	a.qb = q & 3;
+	a.shifted = __any(act && qd != 0);
+	a.unaligned = __any(act && a.qb != 0);
+	a.m1 = opaque((qd & 1) ? ~0u : 0u);
+	a.m2 = opaque((qd & 2) ? ~0u : 0u);
+	Hdr6 h;
+	const uint32_t R0 = rdw(D, 0, a), R1 = rdw(D, 1, a);
+	h.h8 = fold16(hsum(R1, hsum(R0, 0)));
+	h.nh = (R1 >> 16) & 0xffu;
+	h.fl4 = 0;
+	if ((flags & (CGCK_VERIFY | CGCK_ZERO_FIELDS)) && (flags & CGCK_L4)) {
+		// TCP +16 -> byte 56, dword 14 low half; UDP +6 -> 46, dword 11 high;
+		// ICMPv6 +2 -> 42, dword 10 high
+		const uint32_t R10 = rdw(D, 10, a), R11 = rdw(D, 11, a), R14 = rdw(D, 14, a);
+		h.fl4 = h.nh == 6 ? (R14 & 0xffffu) : ((h.nh == 17 ? R11 : R10) >> 16);
+	}
+	return h;
+}
+
+// T: the folded sum over [a0, a0 + len) in the absolute frame.  A wave none of
+// whose packets has an extension or Fragment header finishes in straight-line
+// code; a packet that has one is finished by its own lane from global memory
+// (v6_walk, the words of [40, l4_off) and the field at l4_off + fo read by
+// bytes: exact at any alignment of a0, only slower).  No STORE, no counters
+// (lpw6_ok).  The semantics are cksum6_kernel's (include/cgck.h, CGCK_IP6).
+__device__ __forceinline__ Res result6(const KParams &p, uint64_t a0, int len, uint32_t T, const Hdr6 &h, bool act)
+{
+	const uint32_t flags = p.flags;
+	if (a0 & 1)
+		T = bswap16(T); // packet-relative
+	if (flags & CGCK_RAW)
+		return Res{finish(T), 0};
+	if (len < 40)
+		return Res{0, (uint32_t)CGCK_BAD_LEN};
+	if (!(flags & CGCK_L4))
+		return Res{0, 0}; // CGCK_IP alone: inert
+	const bool zf = flags & (CGCK_VERIFY | CGCK_ZERO_FIELDS);
+	int l4 = 40, st = kV6Ok;
+	uint32_t nh = h.nh, fl4 = h.fl4, ext = 0;
+	const bool chain = act && (v6_is_ext(h.nh) || h.nh == 44);
+	if (__any(chain)) {
+		if (chain) {
+			const V6 v = v6_walk(a0, len, h.nh);
+			l4 = v.l4_off;
+			nh = v.nh;
+			st = v.st;
+			fl4 = 0;
+			if (st == kV6Ok) {
+				// at most 32 Ki words below 0x10000: no overflow
+				for (int o = 40; o < l4; o += 2)
+					ext += (uint32_t)*gbl_at<const uint8_t>(a0 + o) |
+					       (uint32_t)*gbl_at<const uint8_t>(a0 + o + 1) << 8;
+				const int fo = v6_field(nh);
+				if (zf && fo >= 0)
+					fl4 = (uint32_t)*gbl_at<const uint8_t>(a0 + l4 + fo) |
+					      (uint32_t)*gbl_at<const uint8_t>(a0 + l4 + fo + 1) << 8;
+			}
+		}
+	}
+	const int fo = v6_field(nh);
+	if (st == kV6Ok && fo >= 0 && l4 + fo + 2 > len)
+		st = kV6BadLen; // the checksum field does not fit
+	if (st != kV6Ok)
+		return Res{0, st == kV6BadLen ? (uint32_t)CGCK_BAD_LEN : 0u};
+	uint32_t L = ocsub(ocsub(T, h.h8), fold16(ext));
+	if (zf && fo >= 0)
+		L = ocsub(L, fl4);
+	L = fold16(L + (nh << 8) + bswap16((uint32_t)(len - l4) & 0xffffu));
+	const uint32_t hi = finish(L);
+	uint32_t verdict = 0;
+	if ((flags & CGCK_VERIFY) && fo >= 0 && !((flags & CGCK_V_UDP_ZERO_SKIP) && nh == 17 && fl4 == 0) && hi != fl4)
+		verdict = CGCK_BAD_L4;
+	return Res{hi << 16, verdict};
+}
+
+// --------------------------------------------------------------------------
 // Output staging
 // --------------------------------------------------------------------------
 //

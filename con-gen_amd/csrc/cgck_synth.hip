@@ -136,6 +136,46 @@ hipError_t launch_synth_ring(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t
 	return hipGetLastError();
 }
 
+// The IMIX set stamped as IPv6 (cgck_synth_imix_ip6, cgck_synth_imix_ring_ip6):
+// the offsets, lengths and descriptors of the two kernels above (stride 0: the
+// packed cycle), each frame stamped as synth_stamp6_strided_kernel stamps one.
+__global__ __launch_bounds__(256) void synth_imix6_kernel(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t stride,
+							  uint32_t l3_off, uint32_t nh)
+{
+	const int fo = v6_field(nh);
+	for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (uint64_t)gridDim.x * 256) {
+		const uint64_t off = stride ? k * stride : (k / 12) * (uint64_t)kImixCycleBytes + c_imix_off[k % 12];
+		const uint32_t len = c_imix_len[k % 12];
+		uint8_t *ip = base + off + l3_off;
+		ip[0] = 0x60;
+		ip[1] = 0;
+		ip[2] = 0;
+		ip[3] = 0;
+		ip[4] = (uint8_t)((len - 40) >> 8);
+		ip[5] = (uint8_t)(len - 40);
+		ip[6] = (uint8_t)nh;
+		if (fo >= 0 && 40 + fo + 2 <= (int)len) {
+			ip[40 + fo] = 0;
+			ip[40 + fo + 1] = 0;
+		}
+		desc[3 * k + 0] = (uint32_t)off;
+		desc[3 * k + 1] = (uint32_t)(off >> 32);
+		desc[3 * k + 2] = (len << 16) | l3_off;
+	}
+}
+
+// stride 0: the packed set (l3_off 0)
+hipError_t launch_synth_imix6(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t stride, uint32_t l3_off,
+			      uint32_t nh, int num_cus, hipStream_t st)
+{
+	uint64_t want = (n + 255) / 256;
+	int blocks = (int)(want < (uint64_t)num_cus * 8 ? want : (uint64_t)num_cus * 8);
+	if (blocks < 1)
+		blocks = 1;
+	hipLaunchKernelGGL(synth_imix6_kernel, dim3(blocks), dim3(256), 0, st, base, desc, n, stride, l3_off, nh);
+	return hipGetLastError();
+}
+
 hipError_t launch_synth_fill(uint8_t *base, uint64_t nbytes, uint64_t seed, int num_cus, hipStream_t st)
 {
 	uint64_t want = (nbytes / 16 + 255) / 256;

@@ -119,7 +119,14 @@ enum {
  * stored, not counted as bad.
  * Accepted by cgck_strided, cgck_desc and cgck_desc_host (with a burst server
  * open such a batch takes the launch path); cgck_burst_request refuses it with
- * -EINVAL.  The RX / TX windows and the drop-in symbols remain IPv4. */
+ * -EINVAL.  The RX / TX windows and the drop-in symbols remain IPv4.
+ * Native kernels (every other batch runs in the group kernel's IPv6 variant,
+ * cksum6, which has the full semantics): dense strided frames of 1 KiB and more
+ * and aligned strided 40..64 B frames with CGCK_IP / CGCK_L4 only (dstr6; lpd6,
+ * lpa6); and, through cgck_desc, cgck_desc_host or cgck_strided, mixed-length
+ * or mid-size batches (a length hint or ip_len of 256..1023 B: a receive burst
+ * copied back to back or left in ring slots) with any flags but CGCK_STORE and
+ * no `bad` counters (lpw6, streamed through LDS like IPv4's lpw). */
 #define CGCK_GEN_BOTH    (CGCK_IP | CGCK_L4)
 #define CGCK_FILL_BOTH   (CGCK_IP | CGCK_L4 | CGCK_ZERO_FIELDS | CGCK_STORE)
 #define CGCK_VERIFY_BSD  (CGCK_IP | CGCK_L4 | CGCK_VERIFY | CGCK_V_IP_ZERO_IS_FFFF | CGCK_V_UDP_ZERO_SKIP)
@@ -149,7 +156,9 @@ int cgck_ctx_sync(cgck_ctx_t *ctx);
  * tests of every family, A/B runs): "auto" (the default), "group", "lpp",
  * "lpa", "slot2", "dstr", "lpd", "lpw".  A family that cannot take a batch
  * (alignment, flags, lengths) still falls back to one that can, so results
- * stay exact.  -EINVAL for an unknown name. */
+ * stay exact; a CGCK_IP6 batch runs in the family's IPv6 variant ("dstr",
+ * "lpd", "lpa", "lpw", "group") or, where there is none or it cannot take the
+ * batch, in the group kernel's.  -EINVAL for an unknown name. */
 int cgck_ctx_set_kernel(cgck_ctx_t *ctx, const char *family);
 
 /* Device-resident batches.  `out` (u32 per packet: lo16 = IP/RAW result,
@@ -412,6 +421,13 @@ uint64_t cgck_imix_bytes(uint64_t n); /* bytes an n-packet IMIX batch occupies *
  * netmap layout: 2048-byte slots, IPv4 at +14), n * stride bytes of buffer. */
 int cgck_synth_imix_ring(cgck_ctx_t *ctx, void *base, cgck_desc_t *desc, uint64_t n, uint64_t stride,
 			 uint32_t l3_off, uint64_t seed, void *stream);
+/* The two IMIX sets stamped as IPv6: the byte stream, the 12-frame cycle, the
+ * offsets and the descriptors of cgck_synth_imix / cgck_synth_imix_ring, each
+ * frame stamped as cgck_synth_strided_ip6 stamps one (nh <= 255). */
+int cgck_synth_imix_ip6(cgck_ctx_t *ctx, void *base, cgck_desc_t *desc, uint64_t n,
+			uint32_t nh, uint64_t seed, void *stream);
+int cgck_synth_imix_ring_ip6(cgck_ctx_t *ctx, void *base, cgck_desc_t *desc, uint64_t n, uint64_t stride,
+			     uint32_t l3_off, uint32_t nh, uint64_t seed, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* 3. Toeplitz RSS hash (subr.c:482-530, subr.h:370-371) */

@@ -10,6 +10,10 @@ block by launch block on the same device buffers.
 
     python tools/ab_inproc.py --libs con-gen_amd/libcgck_base.so,con-gen_amd/libcgck.so \\
         --workloads 64,imix,1500,rss --rounds 5
+
+imix6 / ring6: the IMIX set stamped as IPv6 (cgck_synth_imix_ip6 / _ring_ip6 of
+the default build fill the buffer; either library may predate them), run with
+CGCK_GEN_BOTH | CGCK_IP6 at the 354 B length hint.
 """
 import argparse
 import ctypes
@@ -74,6 +78,18 @@ def main():
             work[w] = (lambda L, c, buf=buf, desc=desc: L.cgck_desc(
                 c, buf.ptr, desc.ptr, n, cgck.GEN_BOTH, out.ptr, None, None, None), nbytes + 16 * n)
             keep += [buf, desc]
+        elif w in ("imix6", "ring6"):
+            nbytes = cgck.load().cgck_imix_bytes(n)
+            buf, desc = cgck.DeviceBuffer(2048 * n if w == "ring6" else nbytes), cgck.DeviceBuffer(12 * n)
+            if w == "ring6":
+                e0.synth_imix_ring_ip6(buf.ptr, desc.ptr, n, 2048, 14, 6, 0xC0C0)
+            else:
+                e0.synth_imix_ip6(buf.ptr, desc.ptr, n, 6, 0xC0C0)
+            for L, c in zip(libs, ctxs):
+                L.cgck_set_desc_len_hint(c, nbytes // n)
+            work[w] = (lambda L, c, buf=buf, desc=desc: L.cgck_set_desc_layout(c, cgck.LAYOUT_ANY) or L.cgck_desc(
+                c, buf.ptr, desc.ptr, n, cgck.GEN_BOTH | cgck.IP6, out.ptr, None, None, None), nbytes + 16 * n)
+            keep += [buf, desc]
         elif w == "rss":
             nt = 64 << 20
             buf = cgck.DeviceBuffer(12 * nt)
@@ -117,12 +133,14 @@ def main():
                     res[(w, i)].append(algo / (ms.value / args.launches * 1e-3))
     # parity of the two builds on every workload (the same outputs, byte for byte)
     import numpy as np
-    same = {}
+    same, kern = {}, {}
     for w, (fn, _) in work.items():
         got = []
+        kern[w] = []
         for L, c in zip(libs, ctxs):
             assert fn(L, c) == 0, L.cgck_last_error()
             assert L.cgck_ctx_sync(c) == 0
+            kern[w].append(L.cgck_ctx_last_kernel(c).decode())
             h = np.zeros(16 * n, np.uint8)
             out.download(h)
             got.append(h)
@@ -130,8 +148,9 @@ def main():
     table = {}
     for w in work:
         m = [statistics.median(res[(w, i)]) for i in range(2)]
-        table[w] = {"A": m[0] / HBM, "B": m[1] / HBM, "B_over_A": m[1] / m[0], "same_outputs": same[w]}
-        print(f"{w:>5}: A {m[0] / HBM:6.1%}  B {m[1] / HBM:6.1%}  B/A {m[1] / m[0]:.3f}  same outputs {same[w]}",
+        table[w] = {"A": m[0] / HBM, "B": m[1] / HBM, "B_over_A": m[1] / m[0], "same_outputs": same[w],
+                    "kernels": kern[w]}
+        print(f"{w:>5}: A {m[0] / HBM:6.1%}  B {m[1] / HBM:6.1%}  B/A {m[1] / m[0]:.3f}  same outputs {same[w]}  {kern[w][0]} | {kern[w][1]}",
               flush=True)
     print(json.dumps({"libs": paths, "results": table}))
 
