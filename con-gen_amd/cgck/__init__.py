@@ -483,7 +483,8 @@ class Engine:
 
     def set_desc_layout(self, layout):
         """cgck_set_desc_layout: LAYOUT_PACKED for descriptor batches whose
-        frames lie back to back (picks the streaming kernel, lpw)."""
+        frames lie back to back (lpw streams mid-size batches with or without
+        it; a CGCK_STORE batch under it stays on slot2, without it takes lpf)."""
         _check(load().cgck_set_desc_layout(self.ctx, layout), "cgck_set_desc_layout")
 
     def strided(self, base, n, stride, l3_off, ip_len, flags, out=None, verdict=None, bad=None,

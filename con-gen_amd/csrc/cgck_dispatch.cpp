@@ -5,7 +5,7 @@
 // group (>= 1 KiB typical length otherwise, drop-in and window calls),
 // lpd / lpa (aligned fixed-length 20..64-byte strided batches), lpp (small
 // unaligned or descriptor packets), slot2 and lpw (mid-size / mixed lengths;
-// lpw6 for IPv6).  The
+// lpw6 for IPv6, lpf for IPv4 batches that store fields or count bad sums).  The
 // A/B-only variants measured against them (slot, lppp, the other lpp shapes:
 // cgck_lane_lab.inc; the LDS-DMA stream kernels, the probe kernels) are compiled only into
 // libcgck_lab.so (-DCGCK_LAB, tools/Makefile) for tools/ab_inproc.py and
@@ -48,6 +48,8 @@ hipError_t launch_lpw(const KParams &p, int num_cus, hipStream_t st);
 bool lpw_ok(const KParams &p);
 hipError_t launch_lpw6(const KParams &p, int num_cus, hipStream_t st);
 bool lpw6_ok(const KParams &p);
+hipError_t launch_lpf(const KParams &p, int num_cus, hipStream_t st);
+bool lpf_ok(const KParams &p);
 hipError_t launch_dstr(const KParams &p, int num_cus, hipStream_t st);
 bool dstr_ok(const KParams &p);
 #if CGCK_LAB
@@ -71,7 +73,10 @@ hipError_t launch_slotd(const KParams &p, int num_cus, hipStream_t st);
 //     lane per packet over DMA'd windows of a packed step's span (lpw, the
 //     default for descriptor batches of mixed lengths below 1 KiB under
 //     cgck_set_desc_layout(PACKED); lpw6_kernel, cgck_lpw6.hip, for a CGCK_IP6
-//     batch), 11 dense strided frames streamed through
+//     batch; lpf_kernel, cgck_lpf.hip, the same pipeline with the in-place
+//     field stores and the bad counters, for an IPv4 batch with CGCK_STORE or
+//     a `bad` pointer, lpf_ok: no family name or variant number of its own,
+//     "lpw" pins both), 11 dense strided frames streamed through
 //     LDS by DMA, four per step, with a writer wave (dstr, cgck_dense.hip: the
 //     default for strided batches of >= 1 KiB frames it accepts, dstr_ok;
 //     $CGCK_STR_OLD in the lab build: the first stream kernel,
@@ -114,8 +119,16 @@ hipError_t launch_cksum(const KParams &p0, uint32_t len_hint, int num_cus, int k
 	// vs slot2 62.8 %, in 2048 B ring slots at +14 62.0 vs 45.7 %; dense strided
 	// 256 / 576 / 1000 B 69.6 / 73.1 / 74.7 % vs slot2's 52.1 / 56.6 / 48.4 %,
 	// profiles/r02/dma/lpw; 160 B 46.9 vs 59.8 %, 1500 B 75.6 vs group 79.9 %).
-	// The layout hint (kPacked) no longer changes the choice.
-	const bool stream = len_hint >= kLpwFromLen && lpw_ok(p) && (p.desc || p.stride > 0);
+	// The layout hint (kPacked) does not change that choice.  A batch with bad
+	// counters or CGCK_STORE streams through lpf, the same pipeline with those
+	// side effects, instead of falling to slot2 (tools/fill_ab.py,
+	// profiles/lpf/, DESIGN.md §5.7: VERIFY with counters 1.07 vs slot2's 1.28 ms
+	// packed, 1.37 vs 1.49 ms in ring slots; FILL_BOTH in ring slots 2.00 vs 2.14
+	// ms) with one exception: FILL_BOTH on packed frames measured 1.73 vs slot2's
+	// 1.70 ms, so a descriptor batch with CGCK_STORE under the packed layout hint
+	// stays on slot2 (a pinned "lpw" still runs it in lpf).
+	const bool lpf_auto = lpf_ok(p) && !((p.flags & CGCK_STORE) && p.desc && (kernel & kPacked));
+	const bool stream = len_hint >= kLpwFromLen && (lpw_ok(p) || lpf_auto) && (p.desc || p.stride > 0);
 	if (variant == 0 || !known)
 		variant = !lane_ok ? 1 : lpa_ok ? (lpd_ok(p) ? 13 : 10)
 			: len_hint >= kGroupFromLen ? (!p.desc && dstr_ok(p) ? 11 : 1)
@@ -123,7 +136,7 @@ hipError_t launch_cksum(const KParams &p0, uint32_t len_hint, int num_cus, int k
 	if (variant >= 2 && !lane_ok)
 		variant = 1;
 	if (ip6 && variant != 10 && variant != 11 && variant != 13 &&
-	    !(variant == 15 && lpw6_ok(p))) // lpp, slot2 (and the lab's) are IPv4 only
+	    !(variant == 15 && lpw6_ok(p))) // lpp, slot2, lpf (and the lab's) are IPv4 only
 		variant = 1;
 	if (variant == 10 && !lpa_ok)
 		variant = ip6 ? 1 : 2;
@@ -135,7 +148,7 @@ hipError_t launch_cksum(const KParams &p0, uint32_t len_hint, int num_cus, int k
 #endif
 	if (variant == 11 && !dstr_ok(p))
 		variant = 1;
-	if (variant == 15 && !lpw_ok(p))
+	if (variant == 15 && !lpw_ok(p) && !lpf_ok(p))
 		variant = lane_ok ? 9 : 1;
 	bool nt, contig;
 	if (kernel & kExplicit) {
@@ -159,7 +172,7 @@ hipError_t launch_cksum(const KParams &p0, uint32_t len_hint, int num_cus, int k
 	case 13:
 		return launch_lpd(p, num_cus, st);
 	case 15:
-		return ip6 ? launch_lpw6(p, num_cus, st) : launch_lpw(p, num_cus, st);
+		return ip6 ? launch_lpw6(p, num_cus, st) : lpf_ok(p) ? launch_lpf(p, num_cus, st) : launch_lpw(p, num_cus, st);
 	case 11:
 #if CGCK_LAB
 		if (CGCK_ENV("CGCK_STR_OLD") && stream_ok(p)) // the first stream kernel (cgck_stream.hip)

@@ -16,7 +16,8 @@
 //    packet's head lane only.  Slot partial sums are joined by a segmented
 //    suffix reduction towards the head lane.
 //  * lpw_kernel   — one lane per packet over DMA'd windows of a packed batch
-//    (cgck_lpw_kernel.inc; cgck_lpw6.hip compiles it as lpw6_kernel for IPv6).
+//    (cgck_lpw_kernel.inc; cgck_lpw6.hip compiles it as lpw6_kernel for IPv6,
+//    cgck_lpf.hip as lpf_kernel with the in-place stores and the bad counters).
 //
 // Shared per-packet pieces:
 //  * header(): the first 6 chunks realigned to packet-relative dwords
@@ -529,12 +530,15 @@ __global__ __launch_bounds__(256) void slot2_kernel(KParams p)
 // 7 / 9 / 10+ DMA instructions, fewer waves per CU, or the lane-per-packet walk
 // of each window (21-23 %) lose.
 // The kernel's text is cgck_lpw_kernel.inc, compiled here as lpw_kernel and in
-// cgck_lpw6.hip as lpw6_kernel (CGCK_IP6: the same pipeline, an IPv6 finish).
+// cgck_lpw6.hip as lpw6_kernel (CGCK_IP6: the same pipeline, an IPv6 finish)
+// and in cgck_lpf.hip as lpf_kernel (CGCK_STORE and the bad counters).
 #define CGCK_LPW_KERNEL lpw_kernel
 #define CGCK_LPW_IP6 false
+#define CGCK_LPW_FILL false
 #include "cgck_lpw_kernel.inc"
 #undef CGCK_LPW_KERNEL
 #undef CGCK_LPW_IP6
+#undef CGCK_LPW_FILL
 
 // --------------------------------------------------------------------------
 // Launchers

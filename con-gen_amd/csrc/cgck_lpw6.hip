@@ -13,9 +13,11 @@ namespace cgck {
 
 #define CGCK_LPW_KERNEL lpw6_kernel
 #define CGCK_LPW_IP6 true
+#define CGCK_LPW_FILL false
 #include "cgck_lpw_kernel.inc"
 #undef CGCK_LPW_KERNEL
 #undef CGCK_LPW_IP6
+#undef CGCK_LPW_FILL
 
 bool lpw_ok(const KParams &p);
 

@@ -1,10 +1,13 @@
 // cgck_lpw_kernel.inc — the lpw kernel (lane per packet over DMA'd windows of a
 // step's span; the comment above its include in cgck_lane.hip), its window
-// geometry and its step / issue helpers.  One text, two kernels: cgck_lane.hip
-// compiles it as lpw_kernel (CGCK_LPW_IP6 false, IPv4) and cgck_lpw6.hip as
-// lpw6_kernel (true, CGCK_IP6), each in a module of its own, so the IPv4
-// kernel keeps its code (DESIGN.md §5.6).  The includer defines
-// CGCK_LPW_KERNEL and CGCK_LPW_IP6 and has included cgck_lane.h.
+// geometry and its step / issue helpers.  One text, three kernels: cgck_lane.hip
+// compiles it as lpw_kernel (CGCK_LPW_IP6 false, IPv4), cgck_lpw6.hip as
+// lpw6_kernel (true, CGCK_IP6) and cgck_lpf.hip as lpf_kernel (IPv4 with
+// CGCK_LPW_FILL true: the in-place field stores of CGCK_STORE and the bad
+// counters, the comment there), each in a module of its own, so the IPv4
+// kernel keeps its code (DESIGN.md §5.6, §5.7).  The includer defines
+// CGCK_LPW_KERNEL, CGCK_LPW_IP6 and CGCK_LPW_FILL and has included cgck_lane.h.
+// Everything the fill variant adds sits behind `if constexpr (FILL)`.
 #if !CGCK_LAB || !defined(CGCK_LPW_DMA) // compile-time A/B knobs of the lab build only
 #undef CGCK_LPW_DMA
 #define CGCK_LPW_DMA 8
@@ -22,6 +25,37 @@
 #undef CGCK_LPW_PAIR
 #define CGCK_LPW_PAIR 1
 #endif
+// The fill variant's A/B knobs.  CGCK_LPF_NT: the cache policy of the data
+// DMA.  1: nontemporal, as lpw's; 0: cached; 2 (the product): cached for a
+// CGCK_STORE batch, whose lines are then still in the L2 when the fields are
+// stored into them (16M IMIX packets, FILL_BOTH: 2.20 -> 1.73 ms packed, 2.42
+// -> 2.00 ms in ring slots), nontemporal otherwise (VERIFY with counters: 1.06
+// ms against 1.15 cached; profiles/lpf/).  CGCK_LPF_DEFER 1: a step's field
+// stores issued after the next round's DMA (cgck_lpf.hip); 0: at the end of
+// their step, under the counted waits as they stand.
+#if !CGCK_LAB || !defined(CGCK_LPF_NT)
+#undef CGCK_LPF_NT
+#define CGCK_LPF_NT 2
+#endif
+#if !CGCK_LAB || !defined(CGCK_LPF_DEFER)
+#undef CGCK_LPF_DEFER
+#define CGCK_LPF_DEFER 1
+#endif
+// glds16_nt (cgck_device.h) without the nontemporal policy
+__device__ __forceinline__ void glds16_cached(const void *gsrc, uint32_t lds_dst)
+{
+	uint32_t keep;
+	asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+		     "s_mov_b32 m0, %0"
+		     : "=&s"(keep)
+		     : "v"(gsrc), "s"(lds_dst)
+		     : "memory");
+}
+// the data DMA of this batch goes through the cache (the fill variant only)
+__device__ __forceinline__ bool lpw_dma_cached(uint32_t flags)
+{
+	return CGCK_LPW_FILL && (CGCK_LPF_NT == 0 || (CGCK_LPF_NT == 2 && (flags & CGCK_STORE)));
+}
 // LDS index (in 16-byte units) of window chunk idx
 __device__ __forceinline__ int lpw_at(int idx)
 {
@@ -154,9 +188,15 @@ __device__ __forceinline__ void lpw_issue(const KParams &p, uint64_t wb, uint64_
 			src[i] = x < E ? reinterpret_cast<const void *>((d + x) << 4) : zero;
 		}
 		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the table is read: the slot may be refilled
+		if (lpw_dma_cached(p.flags)) {
 #pragma unroll
-		for (int i = 0; i < kLpwDma; ++i)
-			glds16_nt(src[i], base + 1024 * i);
+			for (int i = 0; i < kLpwDma; ++i)
+				glds16_cached(src[i], base + 1024 * i);
+		} else {
+#pragma unroll
+			for (int i = 0; i < kLpwDma; ++i)
+				glds16_nt(src[i], base + 1024 * i);
+		}
 	} else {
 #pragma unroll
 		for (int i = 0; i < kLpwDma; ++i) {
@@ -165,7 +205,11 @@ __device__ __forceinline__ void lpw_issue(const KParams &p, uint64_t wb, uint64_
 #else
 			const uint64_t c = wb + 64 * i + l;
 #endif
-			glds16_nt(live && c < E ? reinterpret_cast<const void *>(c << 4) : zero, base + 1024 * i);
+			const void *src = live && c < E ? reinterpret_cast<const void *>(c << 4) : zero;
+			if (lpw_dma_cached(p.flags))
+				glds16_cached(src, base + 1024 * i);
+			else
+				glds16_nt(src, base + 1024 * i);
 		}
 	}
 	const uint64_t doff = 12 * dfirst + 16 * (uint64_t)l;
@@ -187,10 +231,72 @@ __device__ __forceinline__ DescW lpw_desc_lds(const uint8_t *dslot)
 	return d;
 }
 
+// --- the fill variant's helpers (used under `if constexpr (FILL)` only) ---
+// The wait for the previous round that leaves this round's kLpwDma + 1 DMA
+// instructions and `extra` later VMEM instructions (stores) in flight.
+// `extra` is wave-uniform and never more than the stores really issued after
+// the round waited for (fewer only waits for more).
+__device__ __forceinline__ void lpf_wait(int extra)
+{
+#define CGCK_LPF_WAIT(x)                                                                       \
+	case x:                                                                                \
+		asm volatile("s_waitcnt vmcnt(%0)" ::"i"(kLpwDma + 1 + x) : "memory");         \
+		break;
+	switch (extra < 10 ? extra : 10) {
+		CGCK_LPF_WAIT(1)
+		CGCK_LPF_WAIT(2)
+		CGCK_LPF_WAIT(3)
+		CGCK_LPF_WAIT(4)
+		CGCK_LPF_WAIT(5)
+		CGCK_LPF_WAIT(6)
+		CGCK_LPF_WAIT(7)
+		CGCK_LPF_WAIT(8)
+		CGCK_LPF_WAIT(9)
+		CGCK_LPF_WAIT(10)
+	default:
+		asm volatile("s_waitcnt vmcnt(%0)" ::"i"(kLpwDma + 1) : "memory");
+	}
+#undef CGCK_LPF_WAIT
+}
+
+// One field of a step (the IP checksums at a0 + 10, or the L4 checksums at a0
+// + hl + fo) stored in place, store16's bytes: a 16-bit store, or two byte
+// stores when some lane's address is odd.  Returns the VMEM instructions
+// issued (0, 1 or 2), wave-uniform and exact: the stores are inline assembly
+// executed by all 64 lanes, so the compiler neither drops, merges nor branches
+// over one.  A lane with nothing to store repeats the first storing lane's
+// store (the same value to the same address: harmless, and no address outside
+// a frame is ever written).
+__device__ __forceinline__ int lpf_store_field(bool on, uint64_t addr, uint32_t v)
+{
+	const uint64_t m = __ballot(on);
+	if (!m)
+		return 0;
+	const int f = __ffsll((long long)m) - 1;
+	const uint64_t a = on ? addr : readlane64(addr, f);
+	const uint32_t x = on ? v : (uint32_t)__builtin_amdgcn_readlane((int)v, f);
+	if (__ballot(on && (addr & 1))) {
+		asm volatile("global_store_byte %0, %1, off" ::"v"(a), "v"(x) : "memory");
+		asm volatile("global_store_byte %0, %1, off offset:1" ::"v"(a), "v"(x >> 8) : "memory");
+		return 2;
+	}
+	asm volatile("global_store_short %0, %1, off" ::"v"(a), "v"(x) : "memory");
+	return 1;
+}
+
+// A step's pending field stores: fp bit 0 the IP field (fv's low half to fa),
+// bit 1 the L4 field (fv's high half to fb).
+__device__ __forceinline__ int lpf_store_fields(uint32_t fp, uint64_t fa, uint64_t fb, uint32_t fv)
+{
+	return lpf_store_field(fp & 1, fa, fv & 0xffffu) + lpf_store_field(fp & 2, fb, fv >> 16);
+}
+
 template <bool DESC, int C, bool W>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))) void CGCK_LPW_KERNEL(KParams p)
 {
 	constexpr bool IP6 = CGCK_LPW_IP6; // lpw6_kernel: the IPv6 finish (header6, result6: cgck_lane.h)
+	constexpr bool FILL = CGCK_LPW_FILL; // lpf_kernel: field stores and bad counters (cgck_lpf.hip)
+	static_assert(!(FILL && (IP6 || W)), "lpf is IPv4, one wave");
 	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 	uint8_t *dring = smem + 2 * kLpwSlot; // 2 x 1 KiB descriptor slots (64 lanes x 16 B; 768 B used)
 	uint32_t *so = reinterpret_cast<uint32_t *>(dring + 2 * 1024);
@@ -258,6 +364,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 	int sage = 0;      // waits left that may leave the chunk store in flight
 	uint64_t pf0 = 0;  // its first packet
 	bool pre = false;       // cur's window 0 (with step j + 2's descriptors) already issued
+	// FILL: the last step's field stores, carried in plain scalars until the
+	// next round is issued (or flushed where none comes), the stores issued
+	// after the last round, and the step totals of the bad counters
+	bool fpend = false;
+	uint32_t fp = 0, fv = 0, exprev = 0, nbad_ip = 0, nbad_l4 = 0;
+	uint64_t fa = 0, fb = 0;
 	for (uint64_t j = 0; j < nsteps; ++j) {
 		const uint64_t first = first_of(j);
 		uint32_t acc = 0, corr = 0;
@@ -289,6 +401,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 						ldsd + (uint32_t)((j + 3) & 1) * 1024, zero);
 				++kiss;
 				pre = nx;
+				uint32_t ex = 0; // FILL: stores issued after this round
 				if (pend) {
 					const __amdgpu_buffer_rsrc_t rs = out_rsrc(p.out + pf0, C * 256);
 #pragma unroll
@@ -296,11 +409,26 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 						bstore16<kSc1>(rs, 16 * (64 * i + l), reinterpret_cast<const u32x4_t *>(so)[64 * i + l]);
 					pend = false;
 					sage = 2;
+					if constexpr (FILL)
+						ex = C / 4;
+				}
+				if constexpr (FILL) {
+					if (fpend) { // the previous step's fields: a whole round to land
+						ex += (uint32_t)lpf_store_fields(fp, fa, fb, fv);
+						fpend = false;
+					}
 				}
 				// The wait for the previous round.  A store issued after this
 				// round (sage 2) or after the previous one (sage 1) may stay in
 				// flight: it sits between the two rounds in the in-order count.
-				if (sage > 0) {
+				if constexpr (FILL) {
+					// the stores issued after this round and after the one
+					// waited for (between the two rounds in the in-order
+					// count) may stay in flight; any other store issued since
+					// (a flush) only makes the wait cover more
+					lpf_wait((int)(ex + exprev));
+					exprev = ex;
+				} else if (sage > 0) {
 					--sage;
 					asm volatile("s_waitcnt vmcnt(%0)" ::"i"(kLpwDma + 1 + C / 4) : "memory");
 				} else {
@@ -430,11 +558,13 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 			if (!pre) { // the last round was a zero round: drained before the next issue or a fallback
 				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 				sage = 0; // (a looser count would no longer cover a round)
+				exprev = 0;
 			}
 		} else if (first < p.n) {
 			// not chained: the lane's packet straight from global memory
 			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 			sage = 0;
+			exprev = 0;
 			pre = false;
 			nn = lpw_step<DESC>(p, first_of(j + 2), load_desc<DESC>(p, first_of(j + 2) + l, p.n));
 			const uint4 *c0 = reinterpret_cast<const uint4 *>(cur.a0 & ~(uint64_t)15);
@@ -466,12 +596,42 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 				gbl(p.out)[pf0 + i] = so[i];
 			pend = false;
 		}
+		if constexpr (FILL) {
+			if (fpend) { // no round came: the fields leave before the scalars are reused
+				lpf_store_fields(fp, fa, fb, fv);
+				fpend = false;
+			}
+		}
 		if (first < p.n) {
 			const uint32_t r = fold16(acc) + (0xffffu - fold16(corr));
 			Res res;
-			if constexpr (IP6)
+			if constexpr (IP6) {
 				res = result6(p, cur.a0, cur.len, fold16(r), h6, cur.ok);
-			else
+			} else if constexpr (FILL) {
+				// result() without its stores and atomics: the fields are
+				// stored by lpf_store_fields (its own conditions, below), the
+				// counters summed per step
+				KParams pq = p;
+				pq.flags = p.flags & ~(uint32_t)CGCK_STORE;
+				pq.bad = nullptr;
+				res = result(pq, cur.a0, cur.len, fold16(r), h);
+				const int hl = (int)h.hd * 4;
+				const bool st = cur.ok && (p.flags & CGCK_STORE) && !(p.flags & CGCK_RAW) && cur.len >= 20 &&
+						cur.len >= hl;
+				fp = (st && (p.flags & CGCK_IP) ? 1u : 0u) | (st && (p.flags & CGCK_L4) && h.fo >= 0 ? 2u : 0u);
+				fa = cur.a0 + 10;
+				fb = cur.a0 + (uint64_t)(hl + (h.fo >= 0 ? h.fo : 0));
+				fv = res.out;
+				fpend = __any(fp != 0);
+				if (!CGCK_LPF_DEFER && fpend) {
+					lpf_store_fields(fp, fa, fb, fv);
+					fpend = false;
+				}
+				if (p.bad) {
+					nbad_ip += (uint32_t)__popcll(__ballot(cur.ok && (res.verdict & CGCK_BAD_IP)));
+					nbad_l4 += (uint32_t)__popcll(__ballot(cur.ok && (res.verdict & CGCK_BAD_L4)));
+				}
+			} else
 				res = result(p, cur.a0, cur.len, fold16(r), h);
 			const int slot = (int)(j % C) * 64 + l;
 			so[slot] = res.out;
@@ -501,5 +661,18 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 		cur = nxt;
 		nxt = nn;
 	}
+	if constexpr (FILL) {
+		if (fpend) // the last step's fields
+			lpf_store_fields(fp, fa, fb, fv);
+	}
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	if constexpr (FILL) {
+		// the running counters: one vector atomic per non-zero total
+		if (p.bad && l == 0) {
+			if (nbad_ip)
+				atomicAdd(p.bad + 0, nbad_ip);
+			if (nbad_l4)
+				atomicAdd(p.bad + 1, nbad_l4);
+		}
+	}
 }

@@ -81,7 +81,9 @@ enum {
 	CGCK_ZERO_FIELDS = 1u << 4, /* read the checksum fields as zero: ip+10 and the L4 field by ip_p
 	                               (TCP +16, UDP +6, ICMP +2 after the header) — the "field = 0,
 	                               recompute" step every call site performs */
-	CGCK_STORE       = 1u << 5, /* write out.lo to ip+10 and out.hi to the L4 field (TX fill) */
+	CGCK_STORE       = 1u << 5, /* write out.lo to ip+10 and out.hi to the L4 field (TX fill).  The
+	                               frames of a CGCK_STORE batch must not overlap: the order
+	                               between packets is unspecified */
 	CGCK_VERIFY      = 1u << 6, /* compare with the stored fields (implies ZERO_FIELDS), verdict bits */
 	CGCK_V_IP_ZERO_IS_FFFF = 1u << 7, /* bsd44 ip_input.c:46-48: a received ip_sum of 0 counts as 0xFFFF */
 	CGCK_V_UDP_ZERO_SKIP   = 1u << 8, /* udp_usrreq.c:86: uh_sum == 0 means "not checksummed" */
@@ -154,7 +156,9 @@ void *cgck_ctx_stream(cgck_ctx_t *ctx);
 int cgck_ctx_sync(cgck_ctx_t *ctx);
 /* Pin the context's kernel family instead of the dispatcher's choice (parity
  * tests of every family, A/B runs): "auto" (the default), "group", "lpp",
- * "lpa", "slot2", "dstr", "lpd", "lpw".  A family that cannot take a batch
+ * "lpa", "slot2", "dstr", "lpd", "lpw" ("lpw" covers its fill / counter
+ * variant for IPv4, lpf_kernel, which takes the batches with CGCK_STORE or a
+ * `bad` pointer).  A family that cannot take a batch
  * (alignment, flags, lengths) still falls back to one that can, so results
  * stay exact; a CGCK_IP6 batch runs in the family's IPv6 variant ("dstr",
  * "lpd", "lpa", "lpw", "group") or, where there is none or it cannot take the
@@ -174,8 +178,13 @@ int cgck_desc(cgck_ctx_t *ctx, void *base, const cgck_desc_t *desc, uint64_t n,
 
 /* Shape hint for descriptor batches: their typical (mean) ip_len, default
  * 1500.  Below 1 KiB the lane-per-packet kernel is used (mixed/small packets,
- * e.g. IMIX = 354), from 1 KiB the lane-group kernel.  Any length is still
- * handled correctly; the hint only picks the faster kernel. */
+ * e.g. IMIX = 354), from 1 KiB the lane-group kernel.  From 256 B to 1 KiB
+ * the batch streams through LDS (lpw); so does an IPv4 transmit fill
+ * (CGCK_STORE) or a verify with `bad` counters (lpf, the same pipeline with
+ * those side effects), except a CGCK_STORE batch under CGCK_LAYOUT_PACKED,
+ * which gathers in registers (slot2), the faster of the two on packed frames.
+ * Any length is still handled correctly; the hint only picks the faster
+ * kernel. */
 int cgck_set_desc_len_hint(cgck_ctx_t *ctx, uint32_t max_ip_len);
 
 /* Layout hint for descriptor batches.  CGCK_LAYOUT_PACKED: the frames of a

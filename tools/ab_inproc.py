@@ -14,6 +14,12 @@ block by launch block on the same device buffers.
 imix6 / ring6: the IMIX set stamped as IPv6 (cgck_synth_imix_ip6 / _ring_ip6 of
 the default build fill the buffer; either library may predate them), run with
 CGCK_GEN_BOTH | CGCK_IP6 at the 354 B length hint.
+
+imixfill / ringfill: the imix / ring buffers run with CGCK_FILL_BOTH (in-place
+field stores; the fill is idempotent under ZERO_FIELDS, so repeated launches and
+both libraries write the same bytes).  imixbad: CGCK_VERIFY_TOY with a verdict
+array and a `bad` pointer on a filled buffer.  The parity step also compares a
+64 KiB sample of each workload's frame buffer after each library's launch.
 """
 import argparse
 import ctypes
@@ -78,6 +84,28 @@ def main():
             work[w] = (lambda L, c, buf=buf, desc=desc: L.cgck_desc(
                 c, buf.ptr, desc.ptr, n, cgck.GEN_BOTH, out.ptr, None, None, None), nbytes + 16 * n)
             keep += [buf, desc]
+        elif w in ("imixfill", "ringfill", "imixbad"):
+            nbytes = cgck.load().cgck_imix_bytes(n)
+            buf, desc = cgck.DeviceBuffer(2048 * n if w == "ringfill" else nbytes), cgck.DeviceBuffer(12 * n)
+            if w == "ringfill":
+                e0.synth_imix_ring(buf.ptr, desc.ptr, n, 2048, 14, 0xC0C0)
+            else:
+                e0.synth_imix(buf.ptr, desc.ptr, n, 0xC0C0)
+            for L, c in zip(libs, ctxs):
+                L.cgck_set_desc_len_hint(c, nbytes // n)
+            if w == "imixbad":
+                e0.set_desc_len_hint(nbytes // n)
+                e0.desc(buf.ptr, desc.ptr, n, cgck.FILL_BOTH)
+                ver, bad = cgck.DeviceBuffer(n), cgck.DeviceBuffer(8)
+                cgck.load().cgck_memset(bad.ptr, 0, 8, e0.stream)
+                keep += [ver, bad]
+                work[w] = (lambda L, c, buf=buf, desc=desc, ver=ver, bad=bad: L.cgck_set_desc_layout(
+                    c, cgck.LAYOUT_ANY) or L.cgck_desc(c, buf.ptr, desc.ptr, n, cgck.VERIFY_TOY, out.ptr, ver.ptr,
+                                                       bad.ptr, None), nbytes + 16 * n, buf)
+            else:
+                work[w] = (lambda L, c, buf=buf, desc=desc: L.cgck_set_desc_layout(c, cgck.LAYOUT_ANY) or L.cgck_desc(
+                    c, buf.ptr, desc.ptr, n, cgck.FILL_BOTH, out.ptr, None, None, None), nbytes + 16 * n, buf)
+            keep += [buf, desc]
         elif w in ("imix6", "ring6"):
             nbytes = cgck.load().cgck_imix_bytes(n)
             buf, desc = cgck.DeviceBuffer(2048 * n if w == "ring6" else nbytes), cgck.DeviceBuffer(12 * n)
@@ -118,7 +146,7 @@ def main():
         evs.append((a, b))
     res = {(w, i): [] for w in work for i in range(2)}
     for r in range(args.rounds + 1):
-        for w, (fn, algo) in work.items():
+        for w, (fn, algo, *_) in work.items():
             order = (0, 1) if r % 2 == 0 else (1, 0)
             for i in order:
                 L, c, (a, b) = libs[i], ctxs[i], evs[i]
@@ -134,7 +162,7 @@ def main():
     # parity of the two builds on every workload (the same outputs, byte for byte)
     import numpy as np
     same, kern = {}, {}
-    for w, (fn, _) in work.items():
+    for w, (fn, _, *frames) in work.items():
         got = []
         kern[w] = []
         for L, c in zip(libs, ctxs):
@@ -143,6 +171,10 @@ def main():
             kern[w].append(L.cgck_ctx_last_kernel(c).decode())
             h = np.zeros(16 * n, np.uint8)
             out.download(h)
+            if frames:   # the frame buffer's first 64 KiB after this library's launch
+                fb = np.zeros(64 << 10, np.uint8)
+                frames[0].download(fb)
+                h = np.concatenate([h, fb])
             got.append(h)
         same[w] = bool(np.array_equal(got[0], got[1]))
     table = {}
