@@ -434,8 +434,10 @@ class Engine:
             self.set_kernel(kernel)
 
     def set_kernel(self, family):
-        """cgck_ctx_set_kernel: pin the kernel family ("auto", "group", "lpp",
-        "lpa", "slot2", "dstr", "lpd", "lpw"; the lab build knows more)."""
+        """cgck_ctx_set_kernel: pin the kernel family by its name in kFamilyNames
+        (csrc/cgck_params.h): "auto", "group", "lpp", "slot2", "lpa", "dstr", "lpd",
+        "lpw"; the lab build also "slot", "str", "span", "slotd", "lpp<N>" and
+        bare numbers."""
         _check(load().cgck_ctx_set_kernel(self.ctx, family.encode()), "cgck_ctx_set_kernel")
 
     def close(self):

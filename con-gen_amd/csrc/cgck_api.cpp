@@ -102,22 +102,13 @@ extern "C" int cgck_device_count(void)
 	return n;
 }
 
-// Kernel family by name (cgck_ctx_set_kernel): 0 = the dispatcher's choice.
-// The product library knows its own families; the lab build also the A/B-only
-// ones and raw variant numbers (tools/sweep.py, $CGCK_KERNEL).  -1: unknown.
+// Kernel family by name (cgck_ctx_set_kernel, kFamilyNames).  The product
+// library knows its own families; the lab build also the A/B-only ones and
+// raw numbers (tools/sweep.py, $CGCK_KERNEL).  -1: unknown.
 static int family_of(const char *kf)
 {
-	static const struct {
-		const char *name;
-		int family;
-	} kFamilies[] = {
-		{"auto", 0}, {"group", 1}, {"lpp", 2}, {"slot2", 9}, {"lpa", 10}, {"dstr", 11}, {"lpd", 13}, {"lpw", 15},
-#if CGCK_LAB
-		{"slot", 3}, {"str", 11}, {"span", 12}, {"slotd", 14},
-#endif
-	};
-	for (const auto &f : kFamilies)
-		if (!strcmp(kf, f.name))
+	for (const auto &f : kFamilyNames)
+		if (!strcmp(kf, f.name) && (CGCK_LAB || !f.lab_only))
 			return f.family;
 #if CGCK_LAB
 	if (!strncmp(kf, "lpp", 3))

@@ -62,18 +62,6 @@ namespace cgck {
 
 hipError_t launch_dstr6(const KParams &p, unsigned blocks, hipStream_t st);
 
-bool dstr_ok(const KParams &p)
-{
-	// IPv6 (dstr6_kernel): IP and L4 only (RAW | IP6 reaches the kernels as RAW)
-	if ((p.flags & CGCK_IP6) && (p.ip_len < 40 || (p.flags & ~(uint32_t)(CGCK_IP6 | CGCK_IP | CGCK_L4))))
-		return false;
-	const uint32_t fl = p.flags & ~(uint32_t)CGCK_IP6;
-	const bool flags_ok = fl == CGCK_RAW || (fl && !(fl & ~(uint32_t)(CGCK_IP | CGCK_L4 | CGCK_L4_NOPSEUDO)));
-	return !p.desc && p.n > 0 && p.n < (1ull << 34) && flags_ok && !p.bad && p.out &&
-	       (reinterpret_cast<uintptr_t>(p.out) & 15) == 0 && p.ip_len >= 20 && p.ip_len <= 1520 &&
-	       p.stride <= 1520 && ((reinterpret_cast<uintptr_t>(p.base) | p.stride | p.l3_off) & 3) == 0;
-}
-
 #if CGCK_LAB
 static int env_int(const char *name, int dflt)
 {

@@ -30,7 +30,7 @@ struct cgck_ctx {
 	hipStream_t stream;
 	uint32_t desc_len_hint;
 	uint32_t desc_layout; // CGCK_LAYOUT_*
-	int family; // kernel family: 0 auto, 1 group, 2 lane-per-packet ($CGCK_KERNEL)
+	int family; // enum Family (cgck_params.h), in the lab build with the kNT.. bits ($CGCK_KERNEL)
 	const char *last_kernel; // cgck_ctx_last_kernel
 	// pinned host staging (drop-in calls, deferred TX)
 	uint8_t *h_stage;

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/cgck.h"
+#include "cgck_params.h" // KParams, the flag bits, enum Family, the measured defaults
 
 // Run-time A/B knobs ($CGCK_KERNEL, $CGCK_LPW_WPC, ...) exist only in the lab
 // build (libcgck_lab.so, -DCGCK_LAB): there CGCK_ENV reads the environment;
@@ -19,60 +19,11 @@
 
 namespace cgck {
 
-// Internal flag (never part of the public enum): skip the BAD_LEN rule so the
-// drop-in udp_cksum keeps the pure-function semantics of subr.c:212-223 even
-// for malformed headers.
-constexpr uint32_t kFlagNoLenCheck = 1u << 15;
-// Internal flag of the RX window (cgck_rx_begin): the L4 result of each
-// packet follows its own protocol, as the stack's verifiers do — ICMP (ip_p 1)
-// is in_cksum(ip + hl, len - hl) with its field at +2 (ip_icmp.c:187-189),
-// everything else udp_cksum with the pseudo-header (tcp_input.c:75-78,
-// udp_usrreq.c:86-89).  Group kernel only.
-constexpr uint32_t kFlagL4Auto = 1u << 14;
-// Internal flag of the RX window: descriptor ip_len is the bytes the frame
-// holds after l3_off (ip_input's `len`); the group kernel itself decides, as
-// cgck_rx_begin's host walk used to, which calls the stack can make on the
-// frame (ip_input.c:28-44, 76; tcp_input.c:67; udp_usrreq.c:65;
-// ip_icmp.c:177; gbtcp/inet.c:282-314) and covers min(ntohs(ip_len), len)
-// bytes.  Per frame it writes KParams.meta: kRxOkIp | kRxOkL4 | kRxIcmp,
-// ip_hl * 4 in bits 8-15, ntohs(ip_len) - ip_hl * 4 in bits 16-31.
-constexpr uint32_t kFlagRx = 1u << 13;
-constexpr uint32_t kRxOkIp = 1, kRxOkL4 = 2, kRxIcmp = 4;
-// Internal flag: a host-resident region bound by PCIe round trips (the
-// drop-in symbols' one region): take the group kernel, whose one block reads
-// the region at once, whatever the lane kernels' preconditions say (lpd for
-// a 20-byte in_cksum read its DMA steps over the fabric: 31 vs 14 us).
-constexpr uint32_t kFlagGroup = 1u << 12;
-
-// The flag sets of the windows' requests (cgck_dropin.cpp): every frame of a
-// receive burst (its meta word, both results by ip_p, fields read as zero),
-// and a transmit fill's headers and segments (both fields read as zero;
-// kFlagL4Auto too when the fill holds ICMP messages).  The burst server's
-// one-workgroup body is compiled for each (burst_body_spec, cgck_group.hip).
-constexpr uint32_t kRxFlags = CGCK_IP | CGCK_L4 | CGCK_ZERO_FIELDS | kFlagL4Auto | kFlagRx;
-constexpr uint32_t kTxFlags = CGCK_IP | CGCK_L4 | CGCK_ZERO_FIELDS;
-
 constexpr uint32_t kImixCycleBytes = 4252; // 7*64 + 4*576 + 1500
 
 // Zeroed device bytes per context: 64 lines of 64 B, so dummy loads can be
 // spread over L2 channels instead of all hitting one line.
 constexpr uint32_t kZeroBytes = 64 * 64;
-
-struct KParams {
-	const uint8_t *base;
-	const cgck_desc_t *desc; // nullptr: strided batch
-	uint64_t n;
-	uint64_t stride;
-	uint32_t l3_off;
-	uint32_t ip_len;
-	uint32_t flags;
-	uint32_t *out;
-	uint8_t *verdict;
-	uint32_t *bad;
-	uint32_t contig; // set by the launcher: contiguous block ranges
-	const void *zero; // kZeroBytes zero bytes of device memory (safe target for clamped loads)
-	uint32_t *meta;   // kFlagRx only: one word per packet (see kFlagRx)
-};
 
 // Mailbox of the burst server (cgck_group.hip), in host-coherent pinned
 // memory.  Two request slots, so one request can be in flight while the host
@@ -178,24 +129,6 @@ hipError_t launch_burst_server(BurstBox *box, const uint64_t *door, const uint32
 // device-memory slot (vblk) of its parity, not in the host staging.
 constexpr uint32_t kBurstVram = 1u << 31;
 
-// Kernel selection flags (see cgck_dispatch.cpp) and the measured defaults
-// (tools/sweep.py; profiles/r01).  The group kernel streams whole lines per
-// wave-instruction, so nontemporal loads + contiguous block ranges win
-// (1500 B: 5.79 -> 6.18 TB/s); the lane kernels re-touch each line from
-// several instructions, so they want cached loads (NT: -30..-50 %).
-constexpr int kNT = 16, kContig = 32, kExplicit = 64;
-constexpr int kPacked = 128; // the context's descriptor layout hint is CGCK_LAYOUT_PACKED
-constexpr uint32_t kGroupFromLen = 1024; // typical length from which the group kernel is used
-constexpr uint32_t kLppUpToLen = 128;    // lane-per-packet up to here, lane-per-slot above
-constexpr uint32_t kLpwFromLen = 256;    // back-to-back frames from here stream through LDS (lpw)
-constexpr int kDefaultLppShape = 2;       // see launch_lpp (6 chunks up front, predicated: best on 64 B)
-constexpr bool kDefaultGroupNT = true, kDefaultGroupContig = true;
-constexpr bool kDefaultLaneNT = false, kDefaultLaneContig = false;
-// Dense strided batches of >= 1 KiB frames take dstr_kernel (cgck_dense.hip,
-// LDS-DMA steps of 4 frames with a writer wave): 80.3-82.0 % vs the group
-// kernel's 78.6-81.5 % in the same process (tools/dstr_sweep.sh,
-// profiles/r02/dense/).  The first LDS-DMA stream kernel (cgck_stream.hip,
-// 76.9 % vs 77.9 %) stays in the lab build.
 // Batched Toeplitz hash over dense 12-byte tuples: 0 two-group loop, 2 A/B
 // pipelined (cgck_rss.hip).
 constexpr int kDefaultRssVariant = 2;

@@ -506,4 +506,23 @@ __device__ __forceinline__ uint32_t wave_max_scan_dpp(uint32_t x)
 	return x;
 }
 
+// blocks for n packets at `per` a block: at most cap, at least one (an empty batch still launches)
+inline unsigned grid_blocks(uint64_t n, uint64_t per, uint64_t cap)
+{
+	const uint64_t want = (n + per - 1) / per, g = want < cap ? want : cap;
+	return (unsigned)(g ? g : 1);
+}
+
+// The launch shape of lpw_kernel, lpw6_kernel and lpf_kernel (`slot`: kLpwSlot of
+// their text, cgck_lpw_kernel.inc): one-wave workgroups, wpc per CU, of chunks of
+// kLpwC 64-frame steps; two 8 KiB windows, two 1 KiB descriptor slots, a chunk's
+// staged outputs (and verdicts): 19.3 KiB of LDS per workgroup, 8 per CU.
+constexpr int kLpwC = 4;
+struct LpwShape { dim3 grid; size_t lds; };
+inline LpwShape lpw_shape(const KParams &p, int num_cus, int wpc, int slot)
+{
+	return {dim3(grid_blocks(p.n, 64 * kLpwC, (uint64_t)num_cus * wpc)),
+		(size_t)(2 * slot + 2 * 1024 + kLpwC * 64 * (p.verdict ? 5 : 4))};
+}
+
 } // namespace cgck

@@ -544,13 +544,6 @@ __global__ __launch_bounds__(256) void slot2_kernel(KParams p)
 // Launchers
 // --------------------------------------------------------------------------
 
-// blocks for n packets at `per` a block: at most cap, at least one (an empty batch still launches)
-static unsigned grid_blocks(uint64_t n, uint64_t per, uint64_t cap)
-{
-	const uint64_t want = (n + per - 1) / per, g = want < cap ? want : cap;
-	return (unsigned)(g ? g : 1);
-}
-
 template <bool DESC, int S0, bool CLAMP>
 static hipError_t launch_lpp_t(const KParams &p, int max_blocks, bool nt, hipStream_t st)
 {
@@ -579,23 +572,6 @@ hipError_t launch_lpp(const KParams &p, int num_cus, bool nt, int shape, hipStre
 		return *lab;
 #endif
 	return p.desc ? launch_lpp_t<true, 6, false>(p, mb, nt, st) : launch_lpp_t<false, 6, false>(p, mb, nt, st);
-}
-
-// An IPv6 batch the lane family's variants (lpd6, lpa6) take: at least the
-// fixed header, and IP / L4 only: no field zeroing, verify or store, so no
-// bad counters either (RAW | IP6 reaches the kernels as RAW).
-bool lane6_ok(const KParams &p)
-{
-	return (p.flags & CGCK_IP6) && !(p.flags & ~(uint32_t)(CGCK_IP6 | CGCK_IP | CGCK_L4)) && p.ip_len >= 40;
-}
-
-bool lpd_ok(const KParams &p)
-{
-	// an output array, 16-byte aligned: a chunk's outputs leave as 16-byte stores
-	return !p.desc && !p.verdict && !p.bad && !(p.flags & CGCK_STORE) && p.out &&
-	       (reinterpret_cast<uintptr_t>(p.out) & 15) == 0 && p.ip_len >= 20 && p.ip_len <= 64 &&
-	       p.stride <= 64 && p.stride * 63 + p.ip_len <= 4096 &&
-	       ((reinterpret_cast<uintptr_t>(p.base) | p.stride | p.l3_off) & 15) == 0;
 }
 
 hipError_t launch_lpd(const KParams &p, int num_cus, hipStream_t st)
@@ -695,12 +671,6 @@ hipError_t launch_slot2(const KParams &p, int num_cus, bool nt, hipStream_t st)
 	return p.desc ? launch_slot2_t<true>(p, mb, nt, st) : launch_slot2_t<false>(p, mb, nt, st);
 }
 
-bool lpw_ok(const KParams &p)
-{
-	return !p.bad && !(p.flags & (CGCK_STORE | kFlagNoLenCheck | kFlagL4Auto)) &&
-	       (reinterpret_cast<uintptr_t>(p.desc) & 15) == 0;
-}
-
 hipError_t launch_lpw(const KParams &p, int num_cus, hipStream_t st)
 {
 	static const int wpc = [] { // $CGCK_LPW_WPC: waves per CU
@@ -709,19 +679,17 @@ hipError_t launch_lpw(const KParams &p, int num_cus, hipStream_t st)
 	}();
 	KParams q = p;
 	q.contig = 0;
-	constexpr int C = 4; // 8 KiB windows: 19.3 KiB of LDS per workgroup, 8 per CU
-	const dim3 g(grid_blocks(p.n, 64 * C, (uint64_t)num_cus * wpc));
-	const size_t lds = 2 * kLpwSlot + 2 * 1024 + C * 64 * (p.verdict ? 5 : 4);
+	const LpwShape sh = lpw_shape(p, num_cus, wpc, kLpwSlot);
 #if CGCK_LAB
-	if (const auto lab = launch_lpw_lab(p, q, g, lds, num_cus, wpc, st)) // $CGCK_LPW_*: q.contig, C = 8, lpx, writer
+	if (const auto lab = launch_lpw_lab(p, q, sh.grid, sh.lds, num_cus, wpc, st)) // $CGCK_LPW_*: q.contig, C = 8, lpx, writer
 		return *lab;
 #endif
 	if (p.desc) {
-		CGCK_NOTE_KERNEL("lpw_kernel<true, %d, false>", C);
-		hipLaunchKernelGGL((lpw_kernel<true, C, false>), g, dim3(64), lds, st, q);
+		CGCK_NOTE_KERNEL("lpw_kernel<true, %d, false>", kLpwC);
+		hipLaunchKernelGGL((lpw_kernel<true, kLpwC, false>), sh.grid, dim3(64), sh.lds, st, q);
 	} else {
-		CGCK_NOTE_KERNEL("lpw_kernel<false, %d, false>", C);
-		hipLaunchKernelGGL((lpw_kernel<false, C, false>), g, dim3(64), lds, st, q);
+		CGCK_NOTE_KERNEL("lpw_kernel<false, %d, false>", kLpwC);
+		hipLaunchKernelGGL((lpw_kernel<false, kLpwC, false>), sh.grid, dim3(64), sh.lds, st, q);
 	}
 	return hipGetLastError();
 }

@@ -19,31 +19,18 @@ namespace cgck {
 #undef CGCK_LPW_IP6
 #undef CGCK_LPW_FILL
 
-bool lpw_ok(const KParams &p);
-
-// An IPv6 batch lpw6 takes: what lpw takes (no STORE, no bad counters, no
-// internal flags, 16-byte aligned descriptors) with CGCK_IP6 set.
-bool lpw6_ok(const KParams &p)
-{
-	return (p.flags & CGCK_IP6) && lpw_ok(p);
-}
-
-// launch_lpw's shape: 8 KiB windows, chunks of 4 steps, 19.3 KiB of LDS per
-// workgroup, 8 one-wave workgroups per CU (the product shape only)
+// launch_lpw's shape (lpw_shape, cgck_lane.h) at 8 one-wave workgroups per CU
 hipError_t launch_lpw6(const KParams &p, int num_cus, hipStream_t st)
 {
 	KParams q = p;
 	q.contig = 0;
-	constexpr int C = 4;
-	const uint64_t want = (p.n + 64 * C - 1) / (64 * C), cap = (uint64_t)num_cus * 8;
-	const dim3 g((unsigned)(want < cap ? (want ? want : 1) : cap));
-	const size_t lds = 2 * kLpwSlot + 2 * 1024 + C * 64 * (p.verdict ? 5 : 4);
+	const LpwShape sh = lpw_shape(p, num_cus, 8, kLpwSlot);
 	if (p.desc) {
-		CGCK_NOTE_KERNEL("lpw6_kernel<true, %d, false>", C);
-		hipLaunchKernelGGL((lpw6_kernel<true, C, false>), g, dim3(64), lds, st, q);
+		CGCK_NOTE_KERNEL("lpw6_kernel<true, %d, false>", kLpwC);
+		hipLaunchKernelGGL((lpw6_kernel<true, kLpwC, false>), sh.grid, dim3(64), sh.lds, st, q);
 	} else {
-		CGCK_NOTE_KERNEL("lpw6_kernel<false, %d, false>", C);
-		hipLaunchKernelGGL((lpw6_kernel<false, C, false>), g, dim3(64), lds, st, q);
+		CGCK_NOTE_KERNEL("lpw6_kernel<false, %d, false>", kLpwC);
+		hipLaunchKernelGGL((lpw6_kernel<false, kLpwC, false>), sh.grid, dim3(64), sh.lds, st, q);
 	}
 	return hipGetLastError();
 }

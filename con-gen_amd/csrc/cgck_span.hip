@@ -218,11 +218,6 @@ __global__ __launch_bounds__(256) void span_kernel(KParams p)
 		flush(r1);
 }
 
-bool span_ok(const KParams &p)
-{
-	return p.desc && !(p.flags & (CGCK_STORE | kFlagNoLenCheck | kFlagL4Auto));
-}
-
 hipError_t launch_span(const KParams &p, int num_cus, bool nt, hipStream_t st)
 {
 	// Exactly the resident blocks: every wave owns 1/(grid x 4) of the

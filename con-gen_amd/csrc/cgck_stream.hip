@@ -322,14 +322,6 @@ __global__ __launch_bounds__(256) void stream_lc_kernel(KParams p)
 	}
 }
 
-bool stream_ok(const KParams &p)
-{
-	const uint32_t fl = p.flags;
-	const bool flags_ok = fl == CGCK_RAW || (fl && !(fl & ~(uint32_t)(CGCK_IP | CGCK_L4 | CGCK_L4_NOPSEUDO)));
-	return !p.desc && p.n > 0 && flags_ok && !p.bad && p.ip_len >= 20 && p.ip_len <= 1520 && p.stride <= 1520 &&
-	       ((reinterpret_cast<uintptr_t>(p.base) | p.stride | p.l3_off) & 3) == 0;
-}
-
 hipError_t launch_stream(const KParams &p, int num_cus, hipStream_t st)
 {
 	static const int wpc = [] { // $CGCK_STR_WPC: waves per CU (A/B runs)
