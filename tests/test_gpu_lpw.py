@@ -170,6 +170,7 @@ def test_full_size_imix(lpw, port):
     out = cgck.DeviceBuffer(4 * n)
     ref = cgck.DeviceBuffer(4 * n)
     lpw.synth_imix(buf.ptr, desc.ptr, n, 0xC0C1)
+    lpw.sync()   # the second engine reads the batch on a stream of its own
     e = cgck.Engine(0, kernel="slot2")   # the register-gather path as the second opinion
     e.set_desc_len_hint(nbytes // n)
     e.desc(buf.ptr, desc.ptr, n, cgck.GEN_BOTH, ref.ptr)
