@@ -30,6 +30,7 @@ VERIFY = 1 << 6
 V_IP_ZERO_IS_FFFF = 1 << 7
 V_UDP_ZERO_SKIP = 1 << 8
 IP6 = 1 << 9            # the record at l3_off is an IPv6 header (include/cgck.h, CGCK_IP6)
+MIXED = 1 << 10         # each record is IPv4 or IPv6 by its own version nibble (CGCK_MIXED)
 GEN_BOTH = IP | L4
 FILL_BOTH = IP | L4 | ZERO_FIELDS | STORE
 VERIFY_BSD = IP | L4 | VERIFY | V_IP_ZERO_IS_FFFF | V_UDP_ZERO_SKIP
@@ -37,6 +38,7 @@ VERIFY_TOY = IP | L4 | VERIFY
 BAD_IP = 1
 BAD_L4 = 2
 BAD_LEN = 4
+NOT_IP = 8              # CGCK_MIXED: the record is neither IPv4 nor IPv6
 
 # cgck_dst_entry_t (include/cgck.h): the struct ip_socket fields con-gen.c:344-349 fills.
 DST_DTYPE = np.dtype([("laddr", "<u4"), ("faddr", "<u4"), ("lport", "<u2"), ("fport", "<u2"),
@@ -73,7 +75,7 @@ EXPORTS = (
     "cgck_rx_pending", "cgck_rx_ready", "cgck_tx_pending", "cgck_tx_ready",
     "cgck_window_stats_n", "cgck_thread_bind", "cgck_thread_device",
     "cgck_test_burst_seq", "cgck_test_burst_stale", "cgck_synth_strided_ip6",
-    "cgck_synth_imix_ip6", "cgck_synth_imix_ring_ip6",
+    "cgck_synth_imix_ip6", "cgck_synth_imix_ring_ip6", "cgck_synth_imix_dual",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -134,6 +136,8 @@ def bind(path):
     if hasattr(L, "cgck_synth_imix_ip6"):      # the IPv6 IMIX pair (an older build loads without it)
         L.cgck_synth_imix_ip6.argtypes = [_vp, _vp, _vp, _u64, _u32, _u64, _vp]
         L.cgck_synth_imix_ring_ip6.argtypes = [_vp, _vp, _vp, _u64, _u64, _u32, _u32, _u64, _vp]
+    if hasattr(L, "cgck_synth_imix_dual"):     # the dual-stack IMIX set (an older build loads without it)
+        L.cgck_synth_imix_dual.argtypes = [_vp, _vp, _vp, _u64, _u64, _u32, _u64, _vp]
     L.cgck_synth_imix.argtypes = [_vp, _vp, _vp, _u64, _u64, _vp]
     L.cgck_synth_imix_ring.argtypes = [_vp, _vp, _vp, _u64, _u64, _u32, _u64, _vp]
     L.cgck_imix_bytes.restype = _u64
@@ -535,6 +539,12 @@ class Engine:
         """cgck_synth_imix_ring_ip6: the synth_imix_ring frames stamped as IPv6."""
         _check(load().cgck_synth_imix_ring_ip6(self.ctx, base, desc, n, stride, l3_off, nh, seed, stream),
                "cgck_synth_imix_ring_ip6")
+
+    def synth_imix_dual(self, base, desc, n, seed, stride=0, l3_off=0, stream=None):
+        """cgck_synth_imix_dual: the IMIX set, packed (stride 0) or in ring slots, with
+        frame k IPv6 when k % 5 < 2 and its protocol by k % 7 (for MIXED batches)."""
+        _check(load().cgck_synth_imix_dual(self.ctx, base, desc, n, stride, l3_off, seed, stream),
+               "cgck_synth_imix_dual")
 
     def toeplitz(self, data, n, stride, cnt, key, out, mask=0xFFFFFFFF, key_size=None, stream=None):
         """cgck_toeplitz: device data/out, host key.  Asynchronous."""

@@ -237,9 +237,13 @@ static int check_flags(uint32_t *flagsp)
 {
 	const uint32_t flags = *flagsp;
 	const uint32_t known = CGCK_RAW | CGCK_IP | CGCK_L4 | CGCK_L4_NOPSEUDO | CGCK_ZERO_FIELDS |
-			       CGCK_STORE | CGCK_VERIFY | CGCK_V_IP_ZERO_IS_FFFF | CGCK_V_UDP_ZERO_SKIP | CGCK_IP6;
+			       CGCK_STORE | CGCK_VERIFY | CGCK_V_IP_ZERO_IS_FFFF | CGCK_V_UDP_ZERO_SKIP | CGCK_IP6 |
+			       CGCK_MIXED;
 	if (flags & ~known)
 		return set_err(-EINVAL, "cgck: unknown flag bits 0x%x", flags & ~known);
+	if ((flags & CGCK_MIXED) && (flags & (CGCK_RAW | CGCK_IP6 | CGCK_L4_NOPSEUDO | CGCK_STORE)))
+		return set_err(-EINVAL, "cgck: CGCK_MIXED decides the family and the ICMP rule per packet and stores "
+					"nothing: it excludes CGCK_RAW, CGCK_IP6, CGCK_L4_NOPSEUDO and CGCK_STORE");
 	if ((flags & CGCK_RAW) && (flags & ~(CGCK_RAW | CGCK_IP6)))
 		return set_err(-EINVAL, "cgck: the RAW flag excludes every other flag");
 	if ((flags & CGCK_IP6) && (flags & CGCK_L4_NOPSEUDO))
@@ -274,8 +278,8 @@ extern "C" int cgck_strided(cgck_ctx_t *c, void *base, uint64_t n, uint64_t stri
 	int rc = check_flags(&flags);
 	if (rc)
 		return rc;
-	if ((flags & CGCK_IP6) && ip_len > 65535)
-		return set_err(-EINVAL, "cgck_strided: CGCK_IP6 takes ip_len <= 65535 (no jumbograms)");
+	if ((flags & (CGCK_IP6 | CGCK_MIXED)) && ip_len > 65535)
+		return set_err(-EINVAL, "cgck_strided: CGCK_IP6 and CGCK_MIXED take ip_len <= 65535 (no jumbograms)");
 	if (n && !base)
 		return set_err(-EINVAL, "cgck_strided: NULL base");
 	if (ip_len > 0x7fffffffu)
@@ -965,8 +969,8 @@ static int desc_host_impl(cgck_ctx *c, void *base, size_t bytes, const cgck_desc
 	// on the poster's thread.
 	const bool store = flags & CGCK_STORE;
 	const bool in_place = dev_base && (store || pend || burst_layout(pkt_bytes, n).bytes > kServerCopy);
-	// (an IPv6 batch takes the launch path: the server's bodies are IPv4)
-	if (!(flags & CGCK_IP6) && (in_place || !store) &&
+	// (an IPv6 or mixed batch takes the launch path: the server's bodies are IPv4)
+	if (!(flags & (CGCK_IP6 | CGCK_MIXED)) && (in_place || !store) &&
 	    burst_fits(c, n, max_len, in_place ? 0 : pkt_bytes, pkt_bytes)) {
 		// the resident server: no launch, no stream sync
 		const BurstLayout L = burst_layout(in_place ? 0 : pkt_bytes, n);
@@ -1133,13 +1137,13 @@ extern "C" int cgck_burst_request(cgck_ctx_t *c, const void *dev_base, uint64_t 
 {
 	if (!c && !(c = thread_ctx()))
 		return -ENODEV; // thread_ctx set the message
-	const bool ip6 = flags & CGCK_IP6;
+	const bool ip6 = flags & (CGCK_IP6 | CGCK_MIXED);
 	int rc = check_flags(&flags);
 	if (rc)
 		return rc;
 	if (ip6)
-		return set_err(-EINVAL, "cgck_burst_request: the burst server has no IPv6 bodies (CGCK_IP6): use "
-					"cgck_desc_host, which launches such a batch");
+		return set_err(-EINVAL, "cgck_burst_request: the burst server has no IPv6 bodies (CGCK_IP6, CGCK_MIXED): "
+					"use cgck_desc_host, which launches such a batch");
 	if (!dev_base || !range || (n && !desc))
 		return set_err(-EINVAL, "cgck_burst_request: NULL base, zero range or NULL descriptors");
 	if (n == 0)
@@ -1967,6 +1971,23 @@ extern "C" int cgck_synth_imix_ring_ip6(cgck_ctx_t *c, void *base, cgck_desc_t *
 	hipStream_t st = pick(c, stream);
 	HIP_TRY(launch_synth_fill((uint8_t *)base, n * stride, seed, c->num_cus, st));
 	HIP_TRY(launch_synth_imix6((uint8_t *)base, (uint32_t *)desc, n, stride, l3_off, nh, c->num_cus, st));
+	return 0;
+}
+
+extern "C" int cgck_synth_imix_dual(cgck_ctx_t *c, void *base, cgck_desc_t *desc, uint64_t n, uint64_t stride,
+				    uint32_t l3_off, uint64_t seed, void *stream)
+{
+	if (!c || (n && (!base || !desc)))
+		return set_err(-EINVAL, "cgck_synth_imix_dual: bad arguments");
+	if (((uintptr_t)base & 15) || ((uintptr_t)desc & 3))
+		return set_err(-EINVAL, "cgck_synth_imix_dual: misaligned buffers");
+	if (stride ? (l3_off > 0xffff || stride < (uint64_t)l3_off + 1500) : l3_off != 0)
+		return set_err(-EINVAL, "cgck_synth_imix_dual: a slot must hold l3_off + 1500 bytes (stride 0: the packed "
+					"set, l3_off 0)");
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = pick(c, stream);
+	HIP_TRY(launch_synth_fill((uint8_t *)base, stride ? n * stride : cgck_imix_bytes(n), seed, c->num_cus, st));
+	HIP_TRY(launch_synth_dual((uint8_t *)base, (uint32_t *)desc, n, stride, l3_off, c->num_cus, st));
 	return 0;
 }
 

@@ -20,6 +20,7 @@ struct Choice { Kernel kernel; bool nt; bool contig; }; // nt: nontemporal loads
 
 // kernel_bits = Family | kNT | kContig | kExplicit | kPacked | kStrOld;
 // len_hint = the batch's packet length (strided) or typical length (descriptors).
+// Precondition: p.flags has no CGCK_MIXED (launch_cksum sends such a batch to lpwx_kernel first).
 Choice choose(const KParams &p, uint32_t len_hint, int kernel_bits);
 
 } // namespace cgck

@@ -37,6 +37,7 @@ hipError_t launch_lpd(const KParams &p, int num_cus, hipStream_t st);
 hipError_t launch_lpw(const KParams &p, int num_cus, hipStream_t st);
 hipError_t launch_lpw6(const KParams &p, int num_cus, hipStream_t st);
 hipError_t launch_lpf(const KParams &p, int num_cus, hipStream_t st);
+hipError_t launch_lpwx(const KParams &p, int num_cus, hipStream_t st);
 hipError_t launch_dstr(const KParams &p, int num_cus, hipStream_t st);
 #if CGCK_LAB
 hipError_t launch_span(const KParams &p, int num_cus, bool nt, hipStream_t st);
@@ -53,6 +54,9 @@ hipError_t launch_cksum(const KParams &p0, uint32_t len_hint, int num_cus, int k
 {
 	if (p0.n == 0)
 		return hipSuccess;
+	// a CGCK_MIXED batch has one kernel, whatever is pinned: choose() never sees it
+	if (p0.flags & CGCK_MIXED)
+		return launch_lpwx(p0, num_cus, st);
 	// $CGCK_STR_OLD (lab build): the first stream kernel (cgck_stream.hip) for kDstr
 	const Choice c = choose(p0, len_hint, (kernel & ~kStrOld) | (CGCK_ENV("CGCK_STR_OLD") ? kStrOld : 0));
 	KParams p = p0;

@@ -196,5 +196,7 @@ hipError_t launch_synth_ring(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t
 			     hipStream_t st);
 hipError_t launch_synth_imix6(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t stride, uint32_t l3_off,
 			      uint32_t nh, int num_cus, hipStream_t st);
+hipError_t launch_synth_dual(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t stride, uint32_t l3_off, int num_cus,
+			     hipStream_t st);
 
 } // namespace cgck

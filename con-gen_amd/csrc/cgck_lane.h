@@ -180,7 +180,12 @@ struct Res {
 // Finish one packet: T = folded sum over [ip, ip+len) in the ABSOLUTE frame.
 // In-place field stores (CGCK_STORE) and the bad counters happen here; the
 // per-packet outputs are returned for the caller to emit (or stage).
-__device__ __forceinline__ Res result(const KParams &p, uint64_t a0, int len, uint32_t T, const Hdr &h)
+// AUTO (lpwx_kernel, CGCK_MIXED): p.flags carry kFlagL4Auto and the pseudo-header
+// follows the packet's own ip_p (l4_nopseudo, cgck_device.h), as header()'s
+// field offset already does; result() below is the form every other caller
+// compiles.
+template <bool AUTO>
+__device__ __forceinline__ Res result_t(const KParams &p, uint64_t a0, int len, uint32_t T, const Hdr &h)
 {
 	const uint32_t flags = p.flags;
 	if (a0 & 1)
@@ -209,7 +214,7 @@ __device__ __forceinline__ Res result(const KParams &p, uint64_t a0, int len, ui
 			lo = finish(IPs);
 		if (flags & CGCK_L4) {
 			uint32_t L = ocsub(T, IPs);
-			if (!(flags & CGCK_L4_NOPSEUDO))
+			if (!(AUTO ? l4_nopseudo(h.proto, flags) : (flags & CGCK_L4_NOPSEUDO) != 0))
 				L = fold16(L + PS + (h.proto << 8) + bswap16((uint32_t)(len - hl) & 0xffffu));
 			hi = finish(L);
 		}
@@ -238,6 +243,11 @@ __device__ __forceinline__ Res result(const KParams &p, uint64_t a0, int len, ui
 			atomicAdd(p.bad + 1, 1u);
 	}
 	return Res{lo | (hi << 16), verdict};
+}
+
+__device__ __forceinline__ Res result(const KParams &p, uint64_t a0, int len, uint32_t T, const Hdr &h)
+{
+	return result_t<false>(p, a0, len, T, h);
 }
 
 __device__ __forceinline__ void emit(const KParams &p, uint64_t k, const Res &r)
@@ -513,7 +523,7 @@ inline unsigned grid_blocks(uint64_t n, uint64_t per, uint64_t cap)
 	return (unsigned)(g ? g : 1);
 }
 
-// The launch shape of lpw_kernel, lpw6_kernel and lpf_kernel (`slot`: kLpwSlot of
+// The launch shape of lpw_kernel, lpw6_kernel, lpf_kernel and lpwx_kernel (`slot`: kLpwSlot of
 // their text, cgck_lpw_kernel.inc): one-wave workgroups, wpc per CU, of chunks of
 // kLpwC 64-frame steps; two 8 KiB windows, two 1 KiB descriptor slots, a chunk's
 // staged outputs (and verdicts): 19.3 KiB of LDS per workgroup, 8 per CU.

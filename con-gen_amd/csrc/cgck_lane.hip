@@ -17,7 +17,8 @@
 //    suffix reduction towards the head lane.
 //  * lpw_kernel   — one lane per packet over DMA'd windows of a packed batch
 //    (cgck_lpw_kernel.inc; cgck_lpw6.hip compiles it as lpw6_kernel for IPv6,
-//    cgck_lpf.hip as lpf_kernel with the in-place stores and the bad counters).
+//    cgck_lpf.hip as lpf_kernel with the in-place stores and the bad counters,
+//    cgck_lpwx.hip as lpwx_kernel with the family chosen per lane, CGCK_MIXED).
 //
 // Shared per-packet pieces:
 //  * header(): the first 6 chunks realigned to packet-relative dwords
@@ -531,14 +532,17 @@ __global__ __launch_bounds__(256) void slot2_kernel(KParams p)
 // of each window (21-23 %) lose.
 // The kernel's text is cgck_lpw_kernel.inc, compiled here as lpw_kernel and in
 // cgck_lpw6.hip as lpw6_kernel (CGCK_IP6: the same pipeline, an IPv6 finish)
-// and in cgck_lpf.hip as lpf_kernel (CGCK_STORE and the bad counters).
+// and in cgck_lpf.hip as lpf_kernel (CGCK_STORE and the bad counters) and in
+// cgck_lpwx.hip as lpwx_kernel (CGCK_MIXED: the family chosen per lane).
 #define CGCK_LPW_KERNEL lpw_kernel
 #define CGCK_LPW_IP6 false
 #define CGCK_LPW_FILL false
+#define CGCK_LPW_MIXED false
 #include "cgck_lpw_kernel.inc"
 #undef CGCK_LPW_KERNEL
 #undef CGCK_LPW_IP6
 #undef CGCK_LPW_FILL
+#undef CGCK_LPW_MIXED
 
 // --------------------------------------------------------------------------
 // Launchers

@@ -14,10 +14,12 @@ namespace cgck {
 #define CGCK_LPW_KERNEL lpw6_kernel
 #define CGCK_LPW_IP6 true
 #define CGCK_LPW_FILL false
+#define CGCK_LPW_MIXED false
 #include "cgck_lpw_kernel.inc"
 #undef CGCK_LPW_KERNEL
 #undef CGCK_LPW_IP6
 #undef CGCK_LPW_FILL
+#undef CGCK_LPW_MIXED
 
 // launch_lpw's shape (lpw_shape, cgck_lane.h) at 8 one-wave workgroups per CU
 hipError_t launch_lpw6(const KParams &p, int num_cus, hipStream_t st)

@@ -1,13 +1,18 @@
 // cgck_lpw_kernel.inc — the lpw kernel (lane per packet over DMA'd windows of a
 // step's span; the comment above its include in cgck_lane.hip), its window
-// geometry and its step / issue helpers.  One text, three kernels: cgck_lane.hip
+// geometry and its step / issue helpers.  One text, four kernels: cgck_lane.hip
 // compiles it as lpw_kernel (CGCK_LPW_IP6 false, IPv4), cgck_lpw6.hip as
-// lpw6_kernel (true, CGCK_IP6) and cgck_lpf.hip as lpf_kernel (IPv4 with
+// lpw6_kernel (true, CGCK_IP6), cgck_lpf.hip as lpf_kernel (IPv4 with
 // CGCK_LPW_FILL true: the in-place field stores of CGCK_STORE and the bad
-// counters, the comment there), each in a module of its own, so the IPv4
-// kernel keeps its code (DESIGN.md §5.6, §5.7).  The includer defines
-// CGCK_LPW_KERNEL, CGCK_LPW_IP6 and CGCK_LPW_FILL and has included cgck_lane.h.
-// Everything the fill variant adds sits behind `if constexpr (FILL)`.
+// counters, the comment there) and cgck_lpwx.hip as lpwx_kernel (CGCK_LPW_MIXED
+// true, CGCK_MIXED: the family and the finish chosen per lane, the comment
+// there), each in a module of its own, so the IPv4 kernel keeps its code
+// (DESIGN.md §5.6, §5.7, §5.8).  The includer defines CGCK_LPW_KERNEL,
+// CGCK_LPW_IP6, CGCK_LPW_FILL and CGCK_LPW_MIXED and has included cgck_lane.h.
+// Everything the fill variant adds sits behind `if constexpr (FILL)`, everything
+// the mixed one adds behind `if constexpr (MIXED)`; the mixed kernel alone has a
+// fourth template parameter, DRING (false: a descriptor array that is not
+// 16-byte aligned, read from global memory each step instead of by DMA).
 #if !CGCK_LAB || !defined(CGCK_LPW_DMA) // compile-time A/B knobs of the lab build only
 #undef CGCK_LPW_DMA
 #define CGCK_LPW_DMA 8
@@ -291,12 +296,64 @@ __device__ __forceinline__ int lpf_store_fields(uint32_t fp, uint64_t fa, uint64
 	return lpf_store_field(fp & 1, fa, fv & 0xffffu) + lpf_store_field(fp & 2, fb, fv >> 16);
 }
 
+// --- the mixed variant's helpers (used under `if constexpr (MIXED)` only) ---
+// The lane's family (the high nibble of its packet's first byte, byte q of
+// header chunk 0; 0 for a lane without a packet byte) and both header decodes,
+// each with its own family's lanes as the activity flag: the wave-uniform
+// paths inside them (shifted, unaligned, all5, the header-length bound) consult
+// only those lanes, and the other family's lanes get values nobody reads.
+// Neither decoder forms a load here: header<8>() has all six header chunks
+// (its fetch of chunks 4..5 is compiled for fewer than six only) and header6()
+// reads registers, so no address is ever built from the other family's fields.
+__device__ __forceinline__ void lpwx_headers(const uint4 (&w8)[8], const LpwStep &s, uint32_t flags, uint32_t &fam,
+					     Hdr &h, Hdr6 &h6)
+{
+	const int qd = s.q >> 2;
+	const uint32_t d0 = qd == 0 ? w8[0].x : qd == 1 ? w8[0].y : qd == 2 ? w8[0].z : w8[0].w;
+	const uint32_t v = (d0 >> (8 * (s.q & 3) + 4)) & 15u;
+	fam = s.ok && s.len > 0 && (v == 4 || v == 6) ? v : 0u;
+	h = header<8, false>(w8, nullptr, s.nch, s.q, s.len, flags | kFlagL4Auto, fam == 4);
+	h6 = header6(w8, s.q, flags, fam == 6);
+}
+
+// The lane's finish by its family: result_t<true>() (the pseudo-header by the
+// packet's own ip_p) or result6() without the UDP zero skip (RFC 8200 §8.1: a
+// zero UDP checksum over IPv6 is compared and comes out bad); neither family:
+// CGCK_NOT_IP, no byte of a packet: CGCK_BAD_LEN.  No stores, and the counters
+// are the caller's (p.bad is not passed on).  result6()'s walk of an extension
+// chain reads global memory only in lanes of its activity flag.
+__device__ __forceinline__ Res lpwx_result(const KParams &p, const LpwStep &s, uint32_t T, uint32_t fam, const Hdr &h,
+					   const Hdr6 &h6)
+{
+	KParams p4 = p, p6 = p;
+	p4.flags = p.flags | kFlagL4Auto;
+	p4.bad = nullptr;
+	p6.flags = p.flags & ~(uint32_t)CGCK_V_UDP_ZERO_SKIP;
+	p6.bad = nullptr;
+	const Res r4 = result_t<true>(p4, s.a0, s.len, T, h);
+	const Res r6 = result6(p6, s.a0, s.len, T, h6, fam == 6);
+	if (s.len <= 0)
+		return Res{0, (uint32_t)CGCK_BAD_LEN};
+	return fam == 4 ? r4 : fam == 6 ? r6 : Res{0, (uint32_t)CGCK_NOT_IP};
+}
+
+#if CGCK_LPW_MIXED
+template <bool DESC, int C, bool W, bool DRING>
+#else
 template <bool DESC, int C, bool W>
+#endif
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))) void CGCK_LPW_KERNEL(KParams p)
 {
 	constexpr bool IP6 = CGCK_LPW_IP6; // lpw6_kernel: the IPv6 finish (header6, result6: cgck_lane.h)
 	constexpr bool FILL = CGCK_LPW_FILL; // lpf_kernel: field stores and bad counters (cgck_lpf.hip)
+	constexpr bool MIXED = CGCK_LPW_MIXED; // lpwx_kernel: both finishes, chosen per lane (cgck_lpwx.hip)
+#if CGCK_LPW_MIXED
+	constexpr bool DR = DESC && DRING; // the descriptors travel by DMA
+#else
+	constexpr bool DR = DESC;
+#endif
 	static_assert(!(FILL && (IP6 || W)), "lpf is IPv4, one wave");
+	static_assert(!(MIXED && (IP6 || FILL || W)), "lpwx decides the family per lane, stores nothing, one wave");
 	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 	uint8_t *dring = smem + 2 * kLpwSlot; // 2 x 1 KiB descriptor slots (64 lanes x 16 B; 768 B used)
 	uint32_t *so = reinterpret_cast<uint32_t *>(dring + 2 * 1024);
@@ -375,6 +432,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 		uint32_t acc = 0, corr = 0;
 		Hdr h{};
 		Hdr6 h6{};
+		uint32_t fam = 0; // MIXED: the lane's family, 4 or 6 (0: neither, or no byte to read it from)
 		if (first < p.n && cur.nwin > 0) {
 			// the header's chunks, loop-carried in native vectors (an array of
 			// uint4, a union type, was put in scratch)
@@ -383,7 +441,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 			for (int u = 0; u < 8; ++u)
 				t8[u] = u32x4_t{0, 0, 0, 0};
 			if (!pre) {
-				lpw_issue<DESC>(p, cur.S, cur.E, true, cur.gather, cur.cs, cur.ce, cur.dl, smem + (kiss & 1) * kLpwSlot,
+				lpw_issue<DR>(p, cur.S, cur.E, true, cur.gather, cur.cs, cur.ce, cur.dl, smem + (kiss & 1) * kLpwSlot,
 						lds0 + (kiss & 1) * kLpwSlot, first_of(j + 2), first_of(j + 2) < p.n,
 						ldsd + (uint32_t)((j + 2) & 1) * 1024, zero);
 				++kiss;
@@ -395,7 +453,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 				const bool nx = !more && first_of(j + 1) < p.n && nxt.nwin > 0;
 				const uint64_t iwb = more ? cur.S + (uint64_t)(t + 1) * kLpwWin : nxt.S;
 				const uint64_t iE = more ? cur.E : nxt.E;
-				lpw_issue<DESC>(p, iwb, iE, more || nx, more ? cur.gather : nxt.gather, more ? cur.cs : nxt.cs,
+				lpw_issue<DR>(p, iwb, iE, more || nx, more ? cur.gather : nxt.gather, more ? cur.cs : nxt.cs,
 						more ? cur.ce : nxt.ce, more ? cur.dl : nxt.dl, smem + (kiss & 1) * kLpwSlot,
 						lds0 + (kiss & 1) * kLpwSlot, first_of(j + 3), !more && first_of(j + 3) < p.n,
 						ldsd + (uint32_t)((j + 3) & 1) * 1024, zero);
@@ -438,8 +496,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 				// DMA; the barrier is kept in the one-wave form as measured)
 				if (!W)
 					__builtin_amdgcn_s_barrier();
-				if (t == 0) // step j + 2's descriptors came with window 0 of this step
-					nn = lpw_step<DESC>(p, first_of(j + 2), lpw_desc_lds<DESC>(dring + ((j + 2) & 1) * 1024));
+				if (t == 0) { // step j + 2's descriptors came with window 0 of this step
+					if constexpr (DR == DESC)
+						nn = lpw_step<DESC>(p, first_of(j + 2), lpw_desc_lds<DESC>(dring + ((j + 2) & 1) * 1024));
+					else // (no ring: a plain load after the wait, which the compiler waits for itself)
+						nn = lpw_step<DESC>(p, first_of(j + 2), load_desc<DESC>(p, first_of(j + 2) + l, p.n));
+				}
 				if (p.contig == 4) // lab $CGCK_LPW_NOCONS: rounds without the per-window work
 					continue;
 				const uint4 *win = reinterpret_cast<const uint4 *>(smem + (kiss & 1) * kLpwSlot); // round kiss - 2
@@ -549,7 +611,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 #pragma unroll
 				for (int u = 0; u < 8; ++u)
 					w8[u] = make_uint4(t8[u].x, t8[u].y, t8[u].z, t8[u].w);
-				if constexpr (IP6)
+				if constexpr (MIXED)
+					lpwx_headers(w8, cur, p.flags, fam, h, h6);
+				else if constexpr (IP6)
 					h6 = header6(w8, cur.q, p.flags, cur.ok);
 				else
 				h = header<8, false>(w8, reinterpret_cast<const uint4 *>(cur.a0 & ~(uint64_t)15), cur.nch, cur.q,
@@ -582,7 +646,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 #pragma unroll
 				for (int u = 0; u < 8; ++u)
 					w8[u] = ldc<false>(c0, u, cnt, p.zero);
-				if constexpr (IP6)
+				if constexpr (MIXED)
+					lpwx_headers(w8, cur, p.flags, fam, h, h6);
+				else if constexpr (IP6)
 					h6 = header6(w8, cur.q, p.flags, cur.ok);
 				else
 				h = header<8, false>(w8, c0, cur.nch, cur.q, cur.len, p.flags, cur.ok);
@@ -605,7 +671,13 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 		if (first < p.n) {
 			const uint32_t r = fold16(acc) + (0xffffu - fold16(corr));
 			Res res;
-			if constexpr (IP6) {
+			if constexpr (MIXED) {
+				res = lpwx_result(p, cur, fold16(r), fam, h, h6);
+				if (p.bad) { // the fill variant's scheme: step totals, added once at the end
+					nbad_ip += (uint32_t)__popcll(__ballot(cur.ok && (res.verdict & CGCK_BAD_IP)));
+					nbad_l4 += (uint32_t)__popcll(__ballot(cur.ok && (res.verdict & CGCK_BAD_L4)));
+				}
+			} else if constexpr (IP6) {
 				res = result6(p, cur.a0, cur.len, fold16(r), h6, cur.ok);
 			} else if constexpr (FILL) {
 				// result() without its stores and atomics: the fields are
@@ -666,7 +738,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W ? 4 : 1))
 			lpf_store_fields(fp, fa, fb, fv);
 	}
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	if constexpr (FILL) {
+	if constexpr (FILL || MIXED) {
 		// the running counters: one vector atomic per non-zero total
 		if (p.bad && l == 0) {
 			if (nbad_ip)

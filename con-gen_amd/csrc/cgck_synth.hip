@@ -176,6 +176,62 @@ hipError_t launch_synth_imix6(uint8_t *base, uint32_t *desc, uint64_t n, uint64_
 	return hipGetLastError();
 }
 
+// The dual-stack IMIX set (cgck_synth_imix_dual): the same offsets, lengths and
+// descriptors; frame k is IPv6 when k % 5 < 2, else IPv4; its protocol by k % 7
+// (0-3 TCP, 4-5 UDP, 6 ICMP / ICMPv6), that protocol's checksum field zeroed
+// when the frame holds it.
+__global__ __launch_bounds__(256) void synth_dual_kernel(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t stride,
+							 uint32_t l3_off)
+{
+	for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (uint64_t)gridDim.x * 256) {
+		const uint64_t off = stride ? k * stride : (k / 12) * (uint64_t)kImixCycleBytes + c_imix_off[k % 12];
+		const uint32_t len = c_imix_len[k % 12];
+		const bool v6 = k % 5 < 2;
+		const uint32_t pk = (uint32_t)(k % 7);
+		const uint32_t proto = pk < 4 ? 6u : pk < 6 ? 17u : v6 ? 58u : 1u;
+		uint8_t *ip = base + off + l3_off;
+		int field; // the L4 checksum field from the first header byte
+		if (v6) {
+			ip[0] = 0x60;
+			ip[1] = 0;
+			ip[2] = 0;
+			ip[3] = 0;
+			ip[4] = (uint8_t)((len - 40) >> 8);
+			ip[5] = (uint8_t)(len - 40);
+			ip[6] = (uint8_t)proto;
+			field = 40 + v6_field(proto);
+		} else {
+			ip[0] = 0x45;
+			ip[1] = 0;
+			ip[2] = (uint8_t)(len >> 8);
+			ip[3] = (uint8_t)len;
+			ip[9] = (uint8_t)proto;
+			ip[10] = 0;
+			ip[11] = 0;
+			field = 20 + (proto == 6 ? 16 : proto == 17 ? 6 : 2);
+		}
+		if (field + 2 <= (int)len) {
+			ip[field] = 0;
+			ip[field + 1] = 0;
+		}
+		desc[3 * k + 0] = (uint32_t)off;
+		desc[3 * k + 1] = (uint32_t)(off >> 32);
+		desc[3 * k + 2] = (len << 16) | l3_off;
+	}
+}
+
+// stride 0: the packed set (l3_off 0)
+hipError_t launch_synth_dual(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t stride, uint32_t l3_off, int num_cus,
+			     hipStream_t st)
+{
+	uint64_t want = (n + 255) / 256;
+	int blocks = (int)(want < (uint64_t)num_cus * 8 ? want : (uint64_t)num_cus * 8);
+	if (blocks < 1)
+		blocks = 1;
+	hipLaunchKernelGGL(synth_dual_kernel, dim3(blocks), dim3(256), 0, st, base, desc, n, stride, l3_off);
+	return hipGetLastError();
+}
+
 hipError_t launch_synth_fill(uint8_t *base, uint64_t nbytes, uint64_t seed, int num_cus, hipStream_t st)
 {
 	uint64_t want = (nbytes / 16 + 255) / 256;

@@ -88,6 +88,7 @@ enum {
 	CGCK_V_IP_ZERO_IS_FFFF = 1u << 7, /* bsd44 ip_input.c:46-48: a received ip_sum of 0 counts as 0xFFFF */
 	CGCK_V_UDP_ZERO_SKIP   = 1u << 8, /* udp_usrreq.c:86: uh_sum == 0 means "not checksummed" */
 	CGCK_IP6         = 1u << 9, /* the record at l3_off is an IPv6 header (40 bytes); see below */
+	CGCK_MIXED       = 1u << 10, /* each record is IPv4 or IPv6 by its own version nibble; see below */
 };
 /* CGCK_IP6.  ip_len (descriptor or strided argument) is the bytes covered from
  * the first header byte, 40 + payload, at most 65535 (no jumbograms); the
@@ -129,7 +130,44 @@ enum {
  * or mid-size batches (a length hint or ip_len of 256..1023 B: a receive burst
  * copied back to back or left in ring slots) with any flags but CGCK_STORE and
  * no `bad` counters (lpw6, streamed through LDS like IPv4's lpw). */
-#define CGCK_GEN_BOTH    (CGCK_IP | CGCK_L4)
+/* CGCK_MIXED.  A receive burst as it comes off a ring: IPv4 and IPv6 frames,
+ * TCP, UDP, ICMP / ICMPv6 and the odd ARP frame in one batch and one call, with
+ * no host-side sort by family.  Each packet is judged by v, the high nibble of
+ * its first byte; ip_len is the bytes covered from the first header byte, as for
+ * either family (at most 65535 for a strided batch).
+ *   ip_len == 0   verdict CGCK_BAD_LEN, out = 0.
+ *   v == 4        the IPv4 semantics of the other flags, exactly as without
+ *                 CGCK_MIXED, except that the L4 result follows the packet's own
+ *                 ip_p: ip_p == 1 (ICMP) is computed as under CGCK_L4_NOPSEUDO,
+ *                 in_cksum(ip + hl, ip_len - hl) with its field at +2; every
+ *                 other protocol with the pseudo-header.  IPv4's BAD_LEN rules.
+ *   v == 6        the CGCK_IP6 semantics above for that packet: CGCK_IP inert
+ *                 (out.lo = 0, never CGCK_BAD_IP), the extension-header walk,
+ *                 the Fragment rule, the field by the terminal nh and the
+ *                 BAD_LEN rules unchanged.
+ *   any other v   out = 0, verdict CGCK_NOT_IP; nothing compared or counted.
+ * CGCK_V_IP_ZERO_IS_FFFF applies to the IPv4 packets (inert for IPv6 anyway).
+ * CGCK_V_UDP_ZERO_SKIP applies to the IPv4 packets only: RFC 8200 §8.1 forbids
+ * a zero UDP checksum over IPv6, so such a packet is compared and comes out
+ * CGCK_BAD_L4 (under CGCK_IP6 alone the flag is honoured as given).
+ * `bad` counters: [0] += bad IPv4 header sums, [1] += bad L4 sums of either
+ * family.
+ * -EINVAL: CGCK_MIXED with CGCK_RAW, CGCK_IP6, CGCK_L4_NOPSEUDO or CGCK_STORE,
+ * or a strided ip_len > 65535.  CGCK_STORE is out of scope on purpose: a
+ * transmit path knows what it built, and sorts its fills by family for free.
+ * Accepted by cgck_strided, cgck_desc (any 4-byte aligned descriptor array) and
+ * cgck_desc_host (with a burst server open such a batch takes the launch path);
+ * cgck_burst_request refuses it with -EINVAL.  The RX / TX windows and the
+ * drop-in symbols are untouched.  One kernel serves every such batch
+ * (lpwx_kernel: lpw's pipeline with the finish chosen per lane), whatever its
+ * lengths and whatever family is pinned; any length is exact.  Measured on 16M
+ * IMIX frames, two in five IPv6, against two calls over host-sorted descriptor
+ * arrays (lpw + lpw6, the sort itself not timed): 0.83 of their time on frames
+ * copied back to back, but 1.05 on frames left in 2048-byte ring slots, where
+ * the one call is the slower route by more than the run's 1.2 % margin (its
+ * second finish costs 4 % over lpw).  The two-call route needs
+ * every packet's first bytes on the host. */
+#define CGCK_GEN_BOTH   (CGCK_IP | CGCK_L4)
 #define CGCK_FILL_BOTH   (CGCK_IP | CGCK_L4 | CGCK_ZERO_FIELDS | CGCK_STORE)
 #define CGCK_VERIFY_BSD  (CGCK_IP | CGCK_L4 | CGCK_VERIFY | CGCK_V_IP_ZERO_IS_FFFF | CGCK_V_UDP_ZERO_SKIP)
 #define CGCK_VERIFY_TOY  (CGCK_IP | CGCK_L4 | CGCK_VERIFY)
@@ -142,6 +180,8 @@ enum {
 	                           (ip_input.c:24-37 drops these before any checksum):
 	                           out = 0, nothing stored, not counted as bad
 	                           (CGCK_IP6: see that flag) */
+	CGCK_NOT_IP  = 1u << 3, /* CGCK_MIXED only: the record's version nibble is neither 4 nor 6
+	                           (an ARP frame, say): out = 0, nothing compared or counted */
 };
 
 /* Error codes are negative errno values; this gives a thread-local message. */
@@ -162,7 +202,8 @@ int cgck_ctx_sync(cgck_ctx_t *ctx);
  * (alignment, flags, lengths) still falls back to one that can, so results
  * stay exact; a CGCK_IP6 batch runs in the family's IPv6 variant ("dstr",
  * "lpd", "lpa", "lpw", "group") or, where there is none or it cannot take the
- * batch, in the group kernel's.  -EINVAL for an unknown name. */
+ * batch, in the group kernel's.  A CGCK_MIXED batch ignores the pin: one
+ * kernel, lpwx_kernel, serves all of them.  -EINVAL for an unknown name. */
 int cgck_ctx_set_kernel(cgck_ctx_t *ctx, const char *family);
 
 /* Device-resident batches.  `out` (u32 per packet: lo16 = IP/RAW result,
@@ -437,6 +478,16 @@ int cgck_synth_imix_ip6(cgck_ctx_t *ctx, void *base, cgck_desc_t *desc, uint64_t
 			uint32_t nh, uint64_t seed, void *stream);
 int cgck_synth_imix_ring_ip6(cgck_ctx_t *ctx, void *base, cgck_desc_t *desc, uint64_t n, uint64_t stride,
 			     uint32_t l3_off, uint32_t nh, uint64_t seed, void *stream);
+/* A dual-stack IMIX set (for CGCK_MIXED): the byte stream, the 12-frame cycle,
+ * the offsets and the descriptors of cgck_synth_imix (stride == 0: packed,
+ * l3_off must be 0, cgck_imix_bytes(n) bytes) or of cgck_synth_imix_ring
+ * (stride != 0: n * stride bytes).  Frame k is stamped IPv6 when k % 5 < 2 (5 is
+ * coprime to 12: every cycle position sees both families), as
+ * cgck_synth_strided_ip6 stamps one, otherwise IPv4 as cgck_synth_strided does.
+ * Its protocol follows k % 7: 0-3 TCP (6), 4-5 UDP (17), 6 ICMP (1 for IPv4, 58
+ * for IPv6); that protocol's checksum field is zeroed when the frame holds it. */
+int cgck_synth_imix_dual(cgck_ctx_t *ctx, void *base, cgck_desc_t *desc, uint64_t n, uint64_t stride,
+			 uint32_t l3_off, uint64_t seed, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* 3. Toeplitz RSS hash (subr.c:482-530, subr.h:370-371) */
