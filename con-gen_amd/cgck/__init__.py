@@ -39,6 +39,11 @@ BAD_IP = 1
 BAD_L4 = 2
 BAD_LEN = 4
 NOT_IP = 8              # CGCK_MIXED: the record is neither IPv4 nor IPv6
+# Per-frame RSS hash (cgck_rss_strided / _desc / _desc_host): hf bits and kind bits.
+RSS_TCP = 1 << 0        # hf: TCP frames hash their ports
+RSS_UDP = 1 << 1        # hf: UDP frames hash their ports
+RSS_L4 = 1 << 4         # kind: the ports were hashed
+RSS_IP6 = 1 << 5        # kind: an IPv6 tuple
 
 # cgck_dst_entry_t (include/cgck.h): the struct ip_socket fields con-gen.c:344-349 fills.
 DST_DTYPE = np.dtype([("laddr", "<u4"), ("faddr", "<u4"), ("lport", "<u2"), ("fport", "<u2"),
@@ -58,6 +63,18 @@ class DstParams(ctypes.Structure):
 DESC_DTYPE = np.dtype([("frame_off", "<u8"), ("l3_off", "<u2"), ("ip_len", "<u2")], align=False)
 assert DESC_DTYPE.itemsize == 12
 
+
+class RssSpec(ctypes.Structure):
+    """cgck_rss_spec_t: key, mask, hashed protocols and queue count of a frame hash."""
+    _fields_ = [("key", ctypes.c_void_p), ("key_size", ctypes.c_int), ("mask", ctypes.c_uint32),
+                ("hf", ctypes.c_uint32), ("queue_num", ctypes.c_uint32)]
+
+
+class RssRes(ctypes.Structure):
+    """cgck_rss_res_t: the optional per-frame outputs and the queue counters."""
+    _fields_ = [("hash", ctypes.c_void_p), ("kind", ctypes.c_void_p), ("queue", ctypes.c_void_p),
+                ("qcount", ctypes.c_void_p)]
+
 # Every symbol include/cgck.h declares (checked by tests/test_abi.py).
 EXPORTS = (
     "in_cksum", "udp_cksum", "cgck_last_error", "cgck_abi_version", "cgck_ctx_create",
@@ -76,6 +93,7 @@ EXPORTS = (
     "cgck_window_stats_n", "cgck_thread_bind", "cgck_thread_device",
     "cgck_test_burst_seq", "cgck_test_burst_stale", "cgck_synth_strided_ip6",
     "cgck_synth_imix_ip6", "cgck_synth_imix_ring_ip6", "cgck_synth_imix_dual",
+    "cgck_rss_strided", "cgck_rss_desc", "cgck_rss_desc_host",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -158,6 +176,11 @@ def bind(path):
     L.rss_hash4.restype = _u32
     L.rss_hash4.argtypes = [_u32, _u32, ctypes.c_uint16, ctypes.c_uint16, _vp, ctypes.c_int]
     L.cgck_toeplitz.argtypes = [_vp, _vp, _u64, _u64, _u32, _vp, ctypes.c_int, _u32, _vp, _vp]
+    if hasattr(L, "cgck_rss_desc"):            # the per-frame hash (an older build loads without it)
+        _spec, _res = ctypes.POINTER(RssSpec), ctypes.POINTER(RssRes)
+        L.cgck_rss_strided.argtypes = [_vp, _vp, _u64, _u64, _u32, _u32, _spec, _res, _vp]
+        L.cgck_rss_desc.argtypes = [_vp, _vp, _vp, _u64, _spec, _res, _vp]
+        L.cgck_rss_desc_host.argtypes = [_vp, _vp, ctypes.c_size_t, _vp, _u64, _spec, _res]
     L.cgck_dst_cache.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32, _vp, _vp]
     L.cgck_dst_cache_host.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32,
                                       ctypes.POINTER(_u32)]
@@ -552,6 +575,35 @@ class Engine:
         _check(load().cgck_toeplitz(self.ctx, data, n, stride, cnt, k.ctypes.data,
                                     len(k) if key_size is None else key_size, mask, out, stream),
                "cgck_toeplitz")
+
+    @staticmethod
+    def rss_spec(key, mask=0xFFFFFFFF, hf=RSS_TCP | RSS_UDP, queue_num=0, key_size=None):
+        """A cgck_rss_spec_t; the key array is kept alive with it."""
+        k = _u8(key)
+        s = RssSpec(k.ctypes.data, len(k) if key_size is None else key_size, mask, hf, queue_num)
+        s._key_ref = k
+        return s
+
+    def rss_strided(self, base, n, stride, l3_off, ip_len, spec, hash=None, kind=None, queue=None,
+                    qcount=None, stream=None):
+        """cgck_rss_strided: device base and outputs (pointers or None).  Asynchronous."""
+        res = RssRes(hash, kind, queue, qcount)
+        _check(load().cgck_rss_strided(self.ctx, base, n, stride, l3_off, ip_len, ctypes.byref(spec),
+                                       ctypes.byref(res), stream), "cgck_rss_strided")
+
+    def rss_desc(self, base, desc, n, spec, hash=None, kind=None, queue=None, qcount=None, stream=None):
+        """cgck_rss_desc: device base, descriptors and outputs.  Asynchronous."""
+        res = RssRes(hash, kind, queue, qcount)
+        _check(load().cgck_rss_desc(self.ctx, base, desc, n, ctypes.byref(spec), ctypes.byref(res), stream),
+               "cgck_rss_desc")
+
+    def rss_desc_host(self, base, desc, spec, hash=None, kind=None, queue=None, qcount=None):
+        """cgck_rss_desc_host: a host-resident burst (numpy) hashed on the device;
+        the outputs are numpy arrays or None, qcount is incremented.  Synchronous."""
+        assert desc.dtype == DESC_DTYPE
+        res = RssRes(*(None if a is None else a.ctypes.data for a in (hash, kind, queue, qcount)))
+        _check(load().cgck_rss_desc_host(self.ctx, base.ctypes.data, base.nbytes, desc.ctypes.data, len(desc),
+                                         ctypes.byref(spec), ctypes.byref(res)), "cgck_rss_desc_host")
 
     @staticmethod
     def dst_params(laddr, faddr, fport, queue_num, queue_id, key=None, key_size=None):

@@ -1776,6 +1776,155 @@ extern "C" int cgck_toeplitz(cgck_ctx_t *c, const void *data, uint64_t n, uint64
 	return rss_note_use(c, st);
 }
 
+// Per-frame hash of a receive burst (cgck_rssf.hip).  The argument rules the
+// three entry points share; `what` names the caller in the message.
+static int rss_frames_check(const char *what, const cgck_ctx *c, const void *base, const cgck_desc_t *desc,
+			    bool by_desc, uint64_t n, const cgck_rss_spec_t *spec, const cgck_rss_res_t *res)
+{
+	if (!c || !spec || !res || !base)
+		return set_err(-EINVAL, "%s: NULL context, spec, res or base", what);
+	if (!spec->key)
+		return set_err(-EINVAL, "%s: NULL key", what);
+	if (by_desc && n && !desc)
+		return set_err(-EINVAL, "%s: NULL descriptors", what);
+	if (by_desc && ((uintptr_t)desc & 3) != 0)
+		return set_err(-EINVAL, "%s: descriptors must be 4-byte aligned", what);
+	if (!res->hash && !res->kind && !res->queue && !res->qcount)
+		return set_err(-EINVAL, "%s: every output is NULL", what);
+	if (spec->hf & ~(uint32_t)(CGCK_RSS_TCP | CGCK_RSS_UDP))
+		return set_err(-EINVAL, "%s: unknown hf bits 0x%x", what, spec->hf & ~(uint32_t)(CGCK_RSS_TCP | CGCK_RSS_UDP));
+	if (spec->queue_num > 128)
+		return set_err(-EINVAL, "%s: queue_num %u above 128 (RSS_QUEUE_ID_MAX)", what, spec->queue_num);
+	if (spec->queue_num == 0 && (res->queue || res->qcount))
+		return set_err(-EINVAL, "%s: queue or qcount given with queue_num 0", what);
+	return 0;
+}
+
+// One launch over device-visible frames; the arrays of `res` are device memory.
+static int rss_frames_run(cgck_ctx *c, RssfParams p, const cgck_rss_spec_t *spec, const cgck_rss_res_t *res,
+			  hipStream_t st)
+{
+	int rc = rss_prepare(c, spec->key, spec->key_size, kRssLdsMaxCnt, st);
+	if (rc)
+		return rc;
+	p.mask = spec->mask;
+	p.hf = spec->hf;
+	p.queue_num = spec->queue_num;
+	p.tab = c->d_rss_tab;
+	p.zero = c->d_zero;
+	p.hash = res->hash;
+	p.kind = res->kind;
+	p.queue = res->queue;
+	p.qcount = res->qcount;
+	HIP_TRY(launch_rssf(p, c->num_cus, st));
+	c->last_kernel = t_kernel;
+	return rss_note_use(c, st);
+}
+
+extern "C" int cgck_rss_strided(cgck_ctx_t *c, const void *base, uint64_t n, uint64_t stride, uint32_t l3_off,
+				uint32_t ip_len, const cgck_rss_spec_t *spec, const cgck_rss_res_t *res, void *stream)
+{
+	int rc = rss_frames_check("cgck_rss_strided", c, base, nullptr, false, n, spec, res);
+	if (rc)
+		return rc;
+	if (ip_len > 65535)
+		return set_err(-EINVAL, "cgck_rss_strided: ip_len %u above 65535 (no jumbograms)", ip_len);
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	RssfParams p = {};
+	p.base = (const uint8_t *)base;
+	p.n = n;
+	p.stride = stride;
+	p.l3_off = l3_off;
+	p.ip_len = ip_len;
+	return rss_frames_run(c, p, spec, res, pick(c, stream));
+}
+
+extern "C" int cgck_rss_desc(cgck_ctx_t *c, const void *base, const cgck_desc_t *desc, uint64_t n,
+			     const cgck_rss_spec_t *spec, const cgck_rss_res_t *res, void *stream)
+{
+	int rc = rss_frames_check("cgck_rss_desc", c, base, desc, true, n, spec, res);
+	if (rc)
+		return rc;
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	RssfParams p = {};
+	p.base = (const uint8_t *)base;
+	p.desc = desc;
+	p.n = n;
+	return rss_frames_run(c, p, spec, res, pick(c, stream));
+}
+
+// Host-resident burst: registered memory read in place, a pageable range copied
+// whole into device scratch; descriptors and outputs through d_aux.  Always a
+// launch on the context's stream (the burst server has no such body).
+extern "C" int cgck_rss_desc_host(cgck_ctx_t *c, const void *base, size_t bytes, const cgck_desc_t *desc, uint64_t n,
+				  const cgck_rss_spec_t *spec, const cgck_rss_res_t *res)
+{
+	int rc = rss_frames_check("cgck_rss_desc_host", c, base, desc, true, n, spec, res);
+	if (rc)
+		return rc;
+	for (uint64_t i = 0; i < n; i++) {
+		const uint64_t end = desc[i].frame_off + desc[i].l3_off + desc[i].ip_len;
+		if (end > bytes || end < desc[i].frame_off)
+			return set_err(-EINVAL, "cgck_rss_desc_host: descriptor %llu reaches past the %zu bytes given",
+				       (unsigned long long)i, bytes);
+	}
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = c->stream;
+	const uint8_t *dev_base = nullptr;
+	if (bytes) {
+		RegRange rr;
+		dev_base = reg_find(base, bytes, &rr) ? rr.dev + ((const uint8_t *)base - rr.lo)
+						      : (const uint8_t *)registered_ptr(const_cast<void *>(base), bytes);
+	}
+	if (!dev_base) {
+		if ((rc = grow_dev((void **)&c->d_bytes, &c->d_bytes_cap, bytes ? bytes : 16)))
+			return rc;
+		if (bytes)
+			HIP_TRY(hipMemcpyAsync(c->d_bytes, base, bytes, hipMemcpyHostToDevice, st));
+		dev_base = c->d_bytes;
+	}
+	// d_aux: descriptors | hash | qcount | kind | queue
+	const uint32_t qn = spec->queue_num;
+	const size_t h_off = (12 * n + 15) & ~(size_t)15, c_off = h_off + 4 * n, k_off = c_off + 4 * 128,
+		     q_off = k_off + ((n + 15) & ~(size_t)15);
+	if ((rc = grow_dev((void **)&c->d_aux, &c->d_aux_cap, q_off + n)))
+		return rc;
+	if (res->qcount && (rc = grow_host((void **)&c->h_out, &c->h_out_cap, 4 * 128)))
+		return rc;
+	HIP_TRY(hipMemcpyAsync(c->d_aux, desc, 12 * n, hipMemcpyHostToDevice, st));
+	cgck_rss_res_t dres = {};
+	dres.hash = res->hash ? (uint32_t *)(c->d_aux + h_off) : nullptr;
+	dres.qcount = res->qcount ? (uint32_t *)(c->d_aux + c_off) : nullptr;
+	dres.kind = res->kind ? c->d_aux + k_off : nullptr;
+	dres.queue = res->queue ? c->d_aux + q_off : nullptr;
+	if (dres.qcount)
+		HIP_TRY(hipMemsetAsync(dres.qcount, 0, 4 * 128, st));
+	RssfParams p = {};
+	p.base = dev_base;
+	p.desc = c->d_aux;
+	p.n = n;
+	if ((rc = rss_frames_run(c, p, spec, &dres, st)))
+		return rc;
+	if (res->hash)
+		HIP_TRY(hipMemcpyAsync(res->hash, dres.hash, 4 * n, hipMemcpyDeviceToHost, st));
+	if (res->kind)
+		HIP_TRY(hipMemcpyAsync(res->kind, dres.kind, n, hipMemcpyDeviceToHost, st));
+	if (res->queue)
+		HIP_TRY(hipMemcpyAsync(res->queue, dres.queue, n, hipMemcpyDeviceToHost, st));
+	if (res->qcount)
+		HIP_TRY(hipMemcpyAsync(c->h_out, dres.qcount, 4 * qn, hipMemcpyDeviceToHost, st));
+	HIP_TRY(CGCK_SYNC(st));
+	for (uint32_t q = 0; res->qcount && q < qn; q++)
+		res->qcount[q] += c->h_out[q];
+	return 0;
+}
+
 extern "C" int cgck_dst_cache(cgck_ctx_t *c, const cgck_dst_params_t *prm, cgck_dst_entry_t *out, uint32_t cap,
 			      uint32_t *count, void *stream)
 {

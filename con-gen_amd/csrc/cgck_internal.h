@@ -167,6 +167,26 @@ struct DstParams {
 	uint64_t *status;        // one look-back word per tile; zeroed per launch
 };
 
+// Per-frame hash of a receive burst (cgck_rssf.hip; include/cgck.h, section 3).
+// desc != nullptr: descriptors, else frame k at base + k * stride + l3_off with
+// ip_len bytes.  `tab` = the 36 x 256 byte tables; `zero` = the context's zero
+// chunk (loads of lanes without a frame byte to read).
+struct RssfParams {
+	const uint8_t *base;
+	const void *desc;
+	uint64_t n;
+	uint64_t stride;
+	uint32_t l3_off, ip_len;
+	uint32_t mask, hf, queue_num;
+	const uint32_t *tab;
+	const void *zero;
+	uint32_t *hash;
+	uint8_t *kind;
+	uint8_t *queue;
+	uint32_t *qcount;
+};
+
+hipError_t launch_rssf(const RssfParams &p, int num_cus, hipStream_t st);
 hipError_t launch_toeplitz(const RssParams &p, int num_cus, hipStream_t st);
 hipError_t launch_dst_cache(const DstParams &p, int num_cus, hipStream_t st);
 uint32_t dst_iters(uint32_t n, uint32_t cap, bool filter, uint64_t pass_lo, uint64_t pass_hi, int num_cus);

@@ -510,6 +510,85 @@ uint32_t rss_hash4(uint32_t laddr, uint32_t faddr, uint16_t lport, uint16_t fpor
 int cgck_toeplitz(cgck_ctx_t *ctx, const void *data, uint64_t n, uint64_t stride, uint32_t cnt,
 		  const unsigned char *key, int key_size, uint32_t mask, uint32_t *out, void *stream);
 
+/* Per-frame hash of a receive burst: the software RSS steer for transports
+ * without hardware RSS (veth, memif, pcap deliver every frame on one queue) and
+ * the audit of an "RSS is invalid" panic (con-gen.c:358).  The kernel finds the
+ * tuple in each frame itself; nothing is parsed, cut out or uploaded by the host.
+ *
+ * Each frame is ip_len bytes at base + frame_off + l3_off (descriptor or strided
+ * argument, as for the checksum calls) and is judged by v, the high nibble of
+ * its first byte b[0], as under CGCK_MIXED.  The header's own length fields
+ * (IPv4 total length, IPv6 payload length) are not consulted: ip_len bounds
+ * every read.
+ *   ip_len == 0   kind = CGCK_BAD_LEN.
+ *   v == 4        hl = (b[0] & 15) * 4.  ip_len < 20, hl < 20 or ip_len < hl:
+ *                 CGCK_BAD_LEN.  The frame is a fragment when
+ *                 ((b[6] << 8 | b[7]) & 0x3FFF) != 0 (MF set or a non-zero
+ *                 offset; DF alone is not a fragment).  A non-fragment with
+ *                 ip_len >= hl + 4 and ip_p == 6 under CGCK_RSS_TCP, or ip_p ==
+ *                 17 under CGCK_RSS_UDP, hashes the 12 bytes b[12..20) ++
+ *                 b[hl..hl+4): kind = CGCK_RSS_L4.  Every other frame hashes the
+ *                 8 bytes b[12..20): kind = 0.  The byte order is rss_hash4's
+ *                 {faddr, laddr, fport, lport} as the receiver sees them
+ *                 (subr.c:506-530): hash & 0x7F of a CGCK_RSS_L4 frame is
+ *                 rss_hash4(ip_dst, ip_src, dport, sport).
+ *   v == 6        the extension-header walk of CGCK_IP6 without its last clause:
+ *                 l4_off = 40, nh = b[6]; Hop-by-Hop (0), Routing (43) and
+ *                 Destination Options (60) advance by (b[1] + 1) * 8, AH (51) by
+ *                 (b[1] + 2) * 4, at most 8 extension headers.  ip_len < 40, an
+ *                 extension header's first two bytes past ip_len, an l4_off past
+ *                 ip_len or a ninth header: CGCK_BAD_LEN.  The checksum-field
+ *                 clause does not apply: a TCP frame cut after its ports still
+ *                 hashes them.  A Fragment header (44) hashes the 32 bytes
+ *                 b[8..40): kind = CGCK_RSS_IP6.  A terminal nh of 6 under
+ *                 CGCK_RSS_TCP, or 17 under CGCK_RSS_UDP, with ip_len >= l4_off
+ *                 + 4 hashes the 36 bytes b[8..40) ++ b[l4_off..l4_off+4): kind =
+ *                 CGCK_RSS_IP6 | CGCK_RSS_L4.  Everything else hashes b[8..40):
+ *                 kind = CGCK_RSS_IP6.  The addresses always come from the fixed
+ *                 header: there is no home-address or routing-header
+ *                 substitution.
+ *   any other v   kind = CGCK_NOT_IP.
+ * A CGCK_BAD_LEN or CGCK_NOT_IP frame has no hash: hash = 0, queue = 0xFF, no
+ * other kind bit, and it is not counted in qcount.
+ * The key follows cgck_toeplitz's rule (key[0..3] always read, zeros after
+ * max(4, key_size) bytes); these calls share the context's table cache, and its
+ * wait on a key change, with cgck_toeplitz and cgck_dst_cache. */
+enum { CGCK_RSS_TCP = 1u << 0, CGCK_RSS_UDP = 1u << 1 };      /* hf: which protocols hash their ports */
+enum { CGCK_RSS_L4 = 1u << 4, CGCK_RSS_IP6 = 1u << 5 };       /* kind bits, beside CGCK_BAD_LEN / CGCK_NOT_IP */
+
+typedef struct cgck_rss_spec {
+	const unsigned char *key; /* host memory, as cgck_toeplitz */
+	int key_size;
+	uint32_t mask;            /* hash[k] = toeplitz & mask (0x7F = rss_hash4's) */
+	uint32_t hf;              /* CGCK_RSS_TCP | CGCK_RSS_UDP; addresses are always hashed */
+	uint32_t queue_num;       /* 0: no queue ids; else 1..128 (RSS_QUEUE_ID_MAX) */
+} cgck_rss_spec_t;
+
+typedef struct cgck_rss_res {   /* each optional (NULL); at least one non-NULL */
+	uint32_t *hash;   /* per frame */
+	uint8_t *kind;    /* per frame */
+	uint8_t *queue;   /* per frame: hash[k] % queue_num, 0xFF for a frame without a hash */
+	uint32_t *qcount; /* u32[queue_num] running counters: [q] += frames steered to q */
+} cgck_rss_res_t;
+
+/* Device-resident bursts (`base`, `desc` and the arrays of `res` are device
+ * memory; `desc` any 4-byte aligned array), asynchronous on `stream` (NULL: the
+ * context's).  One kernel, rssf_kernel, serves both forms.  n == 0 returns 0 and
+ * launches nothing.  -EINVAL: a NULL ctx, spec, res, key or base (with n > 0 a
+ * NULL desc too); every output NULL; unknown hf bits; queue_num > 128; queue or
+ * qcount given with queue_num == 0; a strided ip_len > 65535. */
+int cgck_rss_strided(cgck_ctx_t *ctx, const void *base, uint64_t n, uint64_t stride, uint32_t l3_off,
+		     uint32_t ip_len, const cgck_rss_spec_t *spec, const cgck_rss_res_t *res, void *stream);
+int cgck_rss_desc(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *desc, uint64_t n,
+		  const cgck_rss_spec_t *spec, const cgck_rss_res_t *res, void *stream);
+/* Host-resident burst, synchronous: registered memory is read in place, a
+ * pageable range [base, base + bytes) is copied to the device and hashed there;
+ * the arrays of `res` are host memory (qcount is incremented).  The frame bytes
+ * are not written.  It never goes through the burst server.  -EINVAL as above,
+ * and when a descriptor reaches past `bytes`. */
+int cgck_rss_desc_host(cgck_ctx_t *ctx, const void *base, size_t bytes, const cgck_desc_t *desc, uint64_t n,
+		       const cgck_rss_spec_t *spec, const cgck_rss_res_t *res);
+
 /* One dst-cache entry: the fields thread_init_dst_cache fills in struct
  * ip_socket (con-gen.c:344-349; subr.h:218-228).  16 bytes. */
 typedef struct cgck_dst_entry {
