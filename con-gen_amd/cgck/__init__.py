@@ -94,6 +94,7 @@ EXPORTS = (
     "cgck_test_burst_seq", "cgck_test_burst_stale", "cgck_synth_strided_ip6",
     "cgck_synth_imix_ip6", "cgck_synth_imix_ring_ip6", "cgck_synth_imix_dual",
     "cgck_rss_strided", "cgck_rss_desc", "cgck_rss_desc_host",
+    "cgck_test_burst_route", "cgck_test_burst_route_kind",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -189,6 +190,10 @@ def bind(path):
     if hasattr(L, "cgck_burst_request"):   # ABI additions of round 4 (an older build loads without them)
         L.cgck_burst_request.argtypes = [_vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp]
         L.cgck_host_device_ptr.argtypes = [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]
+    if hasattr(L, "cgck_test_burst_route"):
+        L.cgck_test_burst_route.argtypes = [_u32, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _u64, _u32, _u64, _u32,
+                                            _u32, ctypes.c_char_p, ctypes.c_size_t]
+        L.cgck_test_burst_route_kind.argtypes = [_u32, ctypes.c_char_p, ctypes.c_size_t]
     L.cgck_thread_ctx.restype = _vp
     L.cgck_set_error_handler.restype = None
     L.cgck_set_error_handler.argtypes = [ERROR_FN, _vp]
@@ -273,6 +278,32 @@ def burst_open(max_pkts=4096, max_bytes=4 << 20, idle_ms=0):
 
 def burst_close():
     _check(load().cgck_burst_close(None), "cgck_burst_close")
+
+
+ROUTE_PAGEABLE, ROUTE_REGISTERED, ROUTE_REQUEST = 0, 1, 2
+
+
+def burst_route(max_pkts, max_bytes, mem, lens, flags, posted=False, n1=0):
+    """cgck_test_burst_route: the name of the route a request of packets of
+    `lens` bytes takes on a server opened with (max_pkts, max_bytes); mem is
+    ROUTE_PAGEABLE / ROUTE_REGISTERED (cgck_desc_host) or ROUTE_REQUEST
+    (cgck_burst_request).  Needs no device."""
+    lens = np.asarray(lens, np.int64)
+    name = ctypes.create_string_buffer(64)
+    rc = load().cgck_test_burst_route(max_pkts, max_bytes, mem, int(posted), len(lens), int(lens.max(initial=0)),
+                                      int(((lens + 15) & ~15).sum()), flags, n1, name, len(name))
+    if rc < 0:
+        raise CgckError(f"cgck_test_burst_route failed ({rc})")
+    return name.value.decode()
+
+
+def burst_route_kinds():
+    """cgck_test_burst_route_kind: {kind: a product request reaches it}."""
+    kinds, buf, i = {}, ctypes.create_string_buffer(64), 0
+    while (rc := load().cgck_test_burst_route_kind(i, buf, len(buf))) >= 0:
+        kinds[buf.value.decode()] = bool(rc)
+        i += 1
+    return kinds
 
 
 def last_error():

@@ -619,23 +619,11 @@ static size_t env_size(const char *v, size_t dflt)
 {
 	return v && *v ? (size_t)strtoull(v, nullptr, 0) : dflt;
 }
-static const uint64_t kServerPkts = env_size(CGCK_ENV("CGCK_SERVER_PKTS"), 1u << 20);
-static const size_t kServerCopy = env_size(CGCK_ENV("CGCK_SERVER_COPY"), 32 << 10);
+static const uint64_t kServerPkts = env_size(CGCK_ENV("CGCK_SERVER_PKTS"), kServerPktsDefault);
+static const size_t kServerCopy = env_size(CGCK_ENV("CGCK_SERVER_COPY"), kServerCopyDefault);
 
-// Offsets in the request block of n descriptors and `staged` packet bytes
-// copied into it (0: read in place).
-struct BurstLayout {
-	size_t d_off, p_off, bytes;
-};
-
-static BurstLayout burst_layout(size_t staged, uint64_t n)
-{
-	BurstLayout L;
-	L.d_off = sizeof(BurstReq);
-	L.p_off = (L.d_off + 12 * n + 15) & ~(size_t)15;
-	L.bytes = L.p_off + staged;
-	return L;
-}
+// (BurstLayout, burst_layout and the predicates below: cgck_route.h, which
+// burst_route names a request's route from)
 
 // Does a request of n packets of at most max_len bytes, `data` packet bytes
 // of which `staged` are copied into the block (0 when read in place), go to
@@ -643,8 +631,7 @@ static BurstLayout burst_layout(size_t staged, uint64_t n)
 static bool burst_fits(const cgck_ctx *c, uint64_t n, uint32_t max_len, size_t staged, size_t data)
 {
 	(void)max_len;
-	return c->bbox && n <= c->bmax && n <= kServerPkts && burst_layout(staged, n).bytes <= c->bstage_cap &&
-	       data <= c->bmax_bytes;
+	return c->bbox && burst_fits_caps(c->bmax, kServerPkts, c->bstage_cap, c->bmax_bytes, n, staged, data);
 }
 
 static uint8_t *burst_block(const cgck_ctx *c, uint32_t seq) { return c->bstage + (size_t)(seq & 1) * c->bstage_cap; }
@@ -968,9 +955,9 @@ static int desc_host_impl(cgck_ctx *c, void *base, size_t bytes, const cgck_desc
 	// size: its latency is hidden, and copying the bytes would put them back
 	// on the poster's thread.
 	const bool store = flags & CGCK_STORE;
-	const bool in_place = dev_base && (store || pend || burst_layout(pkt_bytes, n).bytes > kServerCopy);
+	const bool in_place = burst_in_place(dev_base != nullptr, store, pend != nullptr, pkt_bytes, n, kServerCopy);
 	// (an IPv6 or mixed batch takes the launch path: the server's bodies are IPv4)
-	if (!(flags & (CGCK_IP6 | CGCK_MIXED)) && (in_place || !store) &&
+	if (burst_flags_ok(flags, in_place) &&
 	    burst_fits(c, n, max_len, in_place ? 0 : pkt_bytes, pkt_bytes)) {
 		// the resident server: no launch, no stream sync
 		const BurstLayout L = burst_layout(in_place ? 0 : pkt_bytes, n);
@@ -1387,8 +1374,7 @@ extern "C" int cgck_burst_open(cgck_ctx_t *c, uint32_t max_pkts, size_t max_byte
 	HIP_TRY(hipSetDevice(c->device));
 	// the block holds the header, the descriptors and the packet bytes; the
 	// server's first read fetches kBurstFirst bytes whatever the request
-	size_t cap = burst_layout(((max_bytes + 15) & ~(size_t)15) + 16 * (size_t)max_pkts, max_pkts).bytes;
-	cap = (cap < kBurstFirst ? kBurstFirst : cap + 15) & ~(size_t)15;
+	const size_t cap = burst_stage_cap(max_pkts, max_bytes);
 	// two slots of outputs, each for the largest request
 	size_t resp_bytes = 2 * (size_t)burst_resp_slot(max_pkts);
 	unsigned resp_flags = hipHostMallocCoherent;

@@ -389,14 +389,14 @@ __device__ __forceinline__ void burst_part(const BurstReq &h, uint32_t flags, co
 	// (thousands of written-through 4-byte stores leave as as many fabric
 	// writes: 2048 x 1500 B in place 79 -> 86 us, tools/e2e.py)
 	if constexpr (SYS) { // burst_sys_ok: one packet per group covers the part
-		if (h.max_len <= 80)
+		if (burst_g4(h.max_len))
 			cksum_body<4, 2, 1, true, false, LDSD, true, true, false, FL>(p, 0, 1);
 		else
 			cksum_body<16, 6, 1, true, false, LDSD, true, true, false, FL>(p, 0, 1);
 		return;
 	}
 	if constexpr (LDSP) { // a block of <= 8 KiB: at most ~64 small packets
-		if (h.max_len <= 80)
+		if (burst_g4(h.max_len))
 			cksum_body<4, 2, 1, true, false, LDSD, false, true, true, FL>(p, 0, 1);
 		else
 			cksum_body<16, 6, 1, true, false, LDSD, false, true, true, FL>(p, 0, 1);
@@ -404,14 +404,14 @@ __device__ __forceinline__ void burst_part(const BurstReq &h, uint32_t flags, co
 	}
 	// A part the block covers in one pass with one packet per group runs
 	// unrolled once (U = 1): a small request's time is the body's dependent
-	// VALU chain, which four unrolled packets per group quadruple.
-	if (h.max_len <= 80) {
-		if (hi - lo <= 64)
+	// VALU chain, which four unrolled packets per group quadruple (burst_u1).
+	if (burst_g4(h.max_len)) {
+		if (burst_u1(true, hi - lo))
 			cksum_body<4, 2, 1, true, false, LDSD, false, WT, false, FL>(p, 0, 1);
 		else
 			cksum_body<4, 2, 4, true, false, LDSD, false, WT, false, FL>(p, 0, 1);
 	} else {
-		if (hi - lo <= 16)
+		if (burst_u1(false, hi - lo))
 			cksum_body<16, 6, 1, true, false, LDSD, false, WT, false, FL>(p, 0, 1);
 		else
 			cksum_body<16, 6, 4, true, false, LDSD, false, WT, false, FL>(p, 0, 1);
@@ -452,6 +452,9 @@ __device__ __forceinline__ void burst_body(const BurstReq &h, const uint32_t *de
 // in-place fill; any other set, and a two-part request, take the run-time
 // flags.
 // (Lab opts bit 8192: the run-time flags for every request, the A/B.)
+// The switch instantiates templates, so route_spec (cgck_route.cpp), which
+// names a request's route, restates its flag list: a set added here or there
+// is added to the other.
 template <bool LDSD, bool SYS = false, bool LDSP = false>
 __device__ __forceinline__ void burst_body_spec(const BurstReq &h, const uint32_t *desc, uint32_t n, uint32_t *out,
 						uint32_t *meta, uint8_t *verdict, const void *zero, const uint8_t *base,
@@ -489,15 +492,6 @@ __device__ __forceinline__ void burst_body_spec(const BurstReq &h, const uint32_
 	burst_body<LDSD, SYS, LDSP>(h, desc, 0, n, out, meta, verdict, zero, base);
 }
 
-// Can a one-workgroup request of n packets read its packet bytes in place
-// with the system-coherent body?  One packet per lane group must cover each
-// part in one pass (64 groups of 4 lanes up to 80 bytes, 16 of 16 lanes
-// above), with every packet within the body's S * G chunks (1536 bytes).
-__device__ __forceinline__ bool burst_sys_ok(const BurstReq &h, uint32_t n)
-{
-	return h.max_len <= 80 ? n <= 64 : (n <= 16 && h.max_len <= 1520);
-}
-
 // A request header the server can serve: the count it was told, inside the
 // context's capacity and block, descriptors where the host puts them, staged
 // bytes inside the block.
@@ -513,10 +507,6 @@ __device__ __forceinline__ uint64_t burst_limit(const BurstReq &h)
 {
 	return h.base ? h.range : (uint64_t)(h.bytes - h.p_off);
 }
-
-// Descriptors of one slice pass staged in LDS (12 KiB): a slice of more
-// packets runs in passes.
-constexpr uint32_t kSliceLds = 1024;
 
 // Device-memory command words of a server launch (the leader's relay to the
 // other workgroups): dcmd[seq & 1] = seq | n << 32 for every request, in
@@ -728,7 +718,7 @@ __global__ __launch_bounds__(256) void burst_server_kernel(BurstBox *box, const 
 			__syncthreads();
 			ok = burst_hdr_ok(h, n, max_pkts, vram ? kBurstFirst : cap);
 			// (lab opts bit 4096: the scratch copy for every block, the A/B)
-			const bool in_lds = !ok || (h.bytes <= kBurstFirst && !(opts & 4096));
+			const bool in_lds = !ok || (burst_in_lds(h.bytes) && !(opts & 4096));
 			const uint32_t *sd;
 			if (in_lds) {
 				sd = reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(sblock) + sizeof(BurstReq));
@@ -788,7 +778,7 @@ __global__ __launch_bounds__(256) void burst_server_kernel(BurstBox *box, const 
 				// staged packet bytes are read from the LDS or scratch copy;
 				// packet bytes in place by the system-coherent body, or with
 				// plain loads after the acquire (lab opts bit 256: always so)
-				const bool sys = h.base && burst_sys_ok(h, n) && !(opts & 256);
+				const bool sys = h.base && burst_sys_ok(h.max_len, n) && !(opts & 256);
 				if (h.base && !sys)
 					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
 				if (in_lds) {
@@ -826,13 +816,13 @@ __global__ __launch_bounds__(256) void burst_server_kernel(BurstBox *box, const 
 #if CGCK_SERVER_SMALL_ONLY
 			ok = false;
 #else
-			const uint32_t lo = (uint32_t)((uint64_t)n * j / W), hi = (uint32_t)((uint64_t)n * (j + 1) / W);
+			const uint32_t lo = burst_slice_at(n, j, W), hi = burst_slice_at(n, j + 1, W);
 			const uint32_t *sd = reinterpret_cast<const uint32_t *>(req + sizeof(BurstReq));
 			// (a device-memory block holds at most kBurstFirst bytes: no
 			// descriptor read past it, whatever the mailbox word says)
 			ok = n <= max_pkts && (!vram || sizeof(BurstReq) + 12ull * n <= kBurstFirst);
 			for (uint32_t c0 = lo; ok && c0 < hi; c0 += kSliceLds) {
-				const uint32_t c1 = hi - c0 < kSliceLds ? hi : c0 + kSliceLds;
+				const uint32_t c1 = burst_pass_end(c0, hi);
 				const uint32_t nd = 3 * (c1 - c0);
 				const uint4 hv = (c0 == lo && t < 4) ? src[t] : make_uint4(0, 0, 0, 0);
 				for (uint32_t i = t; i < nd; i += 4 * 256) {

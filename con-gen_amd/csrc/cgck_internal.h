@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "cgck_params.h" // KParams, the flag bits, enum Family, the measured defaults
+#include "cgck_route.h"  // the burst server's constants and routing predicates
 
 // Run-time A/B knobs ($CGCK_KERNEL, $CGCK_LPW_WPC, ...) exist only in the lab
 // build (libcgck_lab.so, -DCGCK_LAB): there CGCK_ENV reads the environment;
@@ -39,9 +40,7 @@ constexpr uint32_t kZeroBytes = 64 * 64;
 // request answers with done[j] = seq (release) once its outputs are visible;
 // a workgroup that refuses its slice (burst_hdr_ok / desc_inside) first
 // stores refused[seq & 1] = seq.
-constexpr uint32_t kBurstMaxWG = 32; // workgroups of a server (K)
-constexpr uint32_t kBurstOneWG = 64; // packets one workgroup serves alone (one wide read of the block)
-constexpr uint32_t kBurstPerWG = 64; // packets per workgroup of a wider request (default)
+// (kBurstMaxWG, kBurstOneWG, kBurstPerWG, burst_wgs, kBurstFirst: cgck_route.h)
 struct BurstBox {
 	uint64_t req[2];     // host -> device: seq | n << 32 of the request in slot seq & 1
 	uint32_t stop;       // host -> device: exit now
@@ -60,18 +59,6 @@ static_assert(sizeof(BurstBox) == 64 + 5 * kBurstMaxWG + 32, "mailbox line, the 
 // The seq after s: 1, 2, ..., 0xfffffffe, 1, ...: never 0 (the relay's
 // "nothing posted"), and s & 1 alternates through the wrap.
 __host__ __device__ constexpr uint32_t burst_next(uint32_t s) { return s >= 0xfffffffeu ? 1u : s + 1u; }
-
-// Workgroups that serve a request of n packets on a server of K with `per`
-// packets per workgroup: one up to kBurstOneWG packets (it reads the whole
-// small block in one round trip), then one per `per` packets, at most K.
-// A wide request's packet reads over the fabric are bound by the device's
-// aggregate host-read rate, not by one CU: 2048 x 64 B in place took 25.3 /
-// 31.2 / 44.4 / 43.9 us at 64 / 32 / 16 / 8 packets per workgroup
-// (tools/srvlat, profiles/r03/burst/srvlat_per_wg.log), so 64 it is.
-__host__ __device__ constexpr uint32_t burst_wgs(uint32_t n, uint32_t K, uint32_t per)
-{
-	return n <= kBurstOneWG ? 1u : ((n + per - 1) / per < K ? (n + per - 1) / per : K);
-}
 
 // Header of a request block (the first 64 bytes of the burst staging), then
 // the n descriptors at d_off = 64, then (base == 0) the packet bytes.  A
@@ -94,8 +81,7 @@ struct BurstReq {
 	uint32_t flags2;  // fill sharing one request); 0: every descriptor takes flags
 	uint32_t pad[4];
 };
-static_assert(sizeof(BurstReq) == 64, "one header line");
-constexpr uint32_t kBurstFirst = 8192;
+static_assert(sizeof(BurstReq) == kBurstReqBytes, "one header line");
 
 // Outputs of a server request of n packets, host-coherent and packed by n
 // (not by the server's capacity), so a small request's outputs share one

@@ -662,6 +662,21 @@ int cgck_probe_read(cgck_ctx_t *ctx, const void *src, uint64_t bytes, uint32_t *
  * -EINVAL: no server open, or a posted request not yet collected. */
 int cgck_test_burst_seq(cgck_ctx_t *ctx, uint32_t seq);
 int cgck_test_burst_stale(cgck_ctx_t *ctx, uint32_t from);
+/* The route a host-resident request would take on a burst server opened with
+ * (max_pkts, max_bytes), written into name[cap]: "launch", "refused"
+ * (cgck_burst_request fails), or which of the server's compiled bodies serves
+ * it, e.g. "one/lds/sys/g16u1/fl" or "wide32/slice/inplace/g4u4+u1/rt/2passes"
+ * ("Burst server", has the table).  mem: 0 cgck_desc_host on pageable memory,
+ * 1 on registered memory, 2 cgck_burst_request; posted: a window's posted
+ * request; max_len: the longest ip_len; pkt_bytes: the packets' bytes, each
+ * padded to 16; flags: as posted; n1: a two-part request's split, or 0.
+ * Needs no device and no context.  cgck_test_burst_route_kind writes the i-th
+ * kind of body a name can stand for and returns 1 when a request to this
+ * library can reach it, 0 when only the lab build's options do, -ENOENT past
+ * the last. */
+int cgck_test_burst_route(uint32_t max_pkts, size_t max_bytes, int mem, int posted, uint64_t n, uint32_t max_len,
+                          uint64_t pkt_bytes, uint32_t flags, uint32_t n1, char *name, size_t cap);
+int cgck_test_burst_route_kind(uint32_t i, char *kind, size_t cap);
 
 #ifdef __cplusplus
 }

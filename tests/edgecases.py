@@ -91,18 +91,29 @@ def off_by_one(v):
     return v + 1 if v < 0xFFFF else v - 1   # a checksum is never 0, so neither is this
 
 
-def header4(rng, ip_len, hl, proto):
+def header4(rng, ip_len, hl, proto, sane=False):
+    """Random bytes under ip_v 4, ip_hl, ip_len and ip_p.  sane: also what a
+    receiving stack checks before it asks for a checksum (oracle/stack_replay.c):
+    no fragment (DF alone), a TTL, and where they fit a TCP data offset of 5 and
+    a UDP length of the whole L4 region, so a crafted frame reaches its verdict."""
     f = rng.integers(0, 256, ip_len, dtype=np.uint8)
     f[0] = 0x40 | hl
     f[2], f[3] = ip_len >> 8, ip_len & 255
     f[9] = proto
+    if sane:
+        f[6], f[7], f[8] = 0x40, 0, 64
+        l4 = ip_len - hl * 4
+        if proto == 6 and l4 >= 13:
+            f[hl * 4 + 12] = 0x50 | (int(f[hl * 4 + 12]) & 15)
+        if proto == 17 and l4 >= 6:
+            f[hl * 4 + 4], f[hl * 4 + 5] = l4 >> 8, l4 & 255
     return f
 
 
-def zero_frame(port, rng, ip_len, hl, proto, flags, which):
+def zero_frame(port, rng, ip_len, hl, proto, flags, which, sane=False):
     """A frame whose header sum (which & 1) and L4 sum (which & 2) are multiples
     of 65535 under `flags`; under CGCK_RAW the whole region's sum."""
-    f = header4(rng, ip_len, hl, proto)
+    f = header4(rng, ip_len, hl, proto, sane)
     if flags & cgck.RAW:
         retune(f, 4, one(port, f, cgck.RAW)[0])
         return f
@@ -129,7 +140,7 @@ def verdict4(flags, proto, ip_sum, l4_sum, ip_field, l4_field):
 VERIFY_SETS = (cgck.VERIFY_BSD, cgck.VERIFY_TOY)
 
 
-def stored_frames(port, rng, ip_len, flags):
+def stored_frames(port, rng, ip_len, flags, sane=False):
     """Frames whose checksum fields are planted.  Each carries `want`: the
     intended verdict under VERIFY_BSD and VERIFY_TOY (the pseudo-header choice
     of `flags` added), from the rules, for test_edgecases_cpu.py to hold against
@@ -147,7 +158,7 @@ def stored_frames(port, rng, ip_len, flags):
             break
         fo = field_off(proto, flags)
         for label, dip, dl4 in (("ok", 0, 0), ("l4_off", 0, 1), ("ip_off", 1, 0)):
-            f = header4(rng, ip_len, 5, proto)
+            f = header4(rng, ip_len, 5, proto, sane)
             lo, hi = one(port, f, cf)
             ipf = off_by_one(lo) if dip else lo
             l4f = off_by_one(hi) if dl4 else hi
@@ -156,7 +167,7 @@ def stored_frames(port, rng, ip_len, flags):
                 put16(f, 20 + fo, l4f)
             add(f"{label}/p{proto}", f, proto, lo, hi, ipf, l4f)
         if proto == 17 and fo >= 0:
-            f = header4(rng, ip_len, 5, proto)
+            f = header4(rng, ip_len, 5, proto, sane)
             lo, hi = one(port, f, cf)
             put16(f, 10, lo)
             put16(f, 20 + fo, 0)
@@ -164,7 +175,7 @@ def stored_frames(port, rng, ip_len, flags):
         # where both sums are 0xFFFF: a stored 0xFFFF is right, a stored 0 only by
         # CGCK_V_IP_ZERO_IS_FFFF (IP) or where CGCK_V_UDP_ZERO_SKIP skips it (UDP)
         for ipf, l4f in ((0xFFFF, 0xFFFF), (0, 0), (0, 0xFFFF), (0xFFFF, 0)):
-            f = zero_frame(port, rng, ip_len, 5, proto, flags, 3)
+            f = zero_frame(port, rng, ip_len, 5, proto, flags, 3, sane)
             put16(f, 10, ipf)
             if fo >= 0:
                 put16(f, 20 + fo, l4f)
@@ -173,11 +184,11 @@ def stored_frames(port, rng, ip_len, flags):
     return frames
 
 
-def frames4(port, rng, ip_len, flags):
+def frames4(port, rng, ip_len, flags, sane=False):
     """The IPv4 class list of one length and flag set."""
     assert ip_len >= 20
     raw = bool(flags & cgck.RAW)
-    frames = [Frame(f"hl_sweep:hl{hl}/p{p}", header4(rng, ip_len, hl, p), hl=hl) for hl in range(16) for p in PROTOS]
+    frames = [Frame(f"hl_sweep:hl{hl}/p{p}", header4(rng, ip_len, hl, p, sane), hl=hl) for hl in range(16) for p in PROTOS]
     frames.append(Frame("fill:00", np.zeros(ip_len, np.uint8), lo_ffff=True))
     frames.append(Frame("fill:ff", np.full(ip_len, 0xFF, np.uint8)))
     f = np.full(ip_len, 0xFF, np.uint8)
@@ -188,10 +199,10 @@ def frames4(port, rng, ip_len, flags):
             for hl in ZERO_HLS:
                 if ip_len < (hl * 4 + 22 if which & 2 else max(hl * 4, 20)):
                     continue
-                frames.append(Frame(f"{cls}:hl{hl}/p{p}", zero_frame(port, rng, ip_len, hl, p, flags, which),
+                frames.append(Frame(f"{cls}:hl{hl}/p{p}", zero_frame(port, rng, ip_len, hl, p, flags, which, sane),
                                     lo_ffff=raw or bool(which & 1), hi_ffff=not raw and bool(which & 2)))
     if reads_fields(flags) and not raw:
-        frames += stored_frames(port, rng, ip_len, flags)
+        frames += stored_frames(port, rng, ip_len, flags, sane)
     return frames
 
 
@@ -478,14 +489,190 @@ CELLS = {
 }
 
 
+# ------------------------------------------------------------------ the burst server's cells
+# A server family (test_gpu_server_edgecases.py, test_server_routes_cpu.py) is
+# a way into the resident burst server and the body that serves it there.  Its
+# shapes carry, beside the layout's own arguments, the request plan: the batch
+# goes in consecutive requests of at most `k` frames (requests()) to a server
+# opened for `max_pkts` frames, and every request must take the route `route`
+# (cgck_test_burst_route; "wide*": any number of workgroups).  "{sys}" /
+# "{ldsp}" in a route stand for fl or rt: the body compiled for the flag set,
+# or the run-time one (COMPILED; the LDS-resident body is compiled for CGCK_RAW
+# too).
+SMALL = (20, 41, 64, 80)       # G = 4 bodies: ip_hl 15 with a TCP field at +76 fits 80 bytes
+MID = (41, 64, 99, 576)
+OVER80 = (99, 256, 576)        # every request's max_len above 80, twelve frames within 8 KiB
+BIG = (577, 1500)               # sixteen frames above 8 KiB of block whichever they are
+LONG = (1600, 4000)            # past the S * G = 1536 unrolled bytes: the long-packet loop
+PLAN_KEYS = ("plan_k", "plan_max_pkts", "plan_route")   # (no layout argument is named so)
+SERVER_BYTES = 4 << 20         # cgck_burst_open's max_bytes in every cell
+COMPILED = (cgck.VERIFY_BSD, cgck.FILL_BOTH, GZ)
+RUNTIME = (G, cgck.VERIFY_TOY, NOPS, NOPS_VERIFY, cgck.RAW, cgck.VERIFY_BSD | cgck.STORE)
+NO_STORE = [f for f in COMPILED + RUNTIME if not f & cgck.STORE]   # a pageable CGCK_STORE batch is launched
+IN_PLACE = list(COMPILED + RUNTIME)
+PAGEABLE, REGISTERED, REQUEST = cgck.ROUTE_PAGEABLE, cgck.ROUTE_REGISTERED, cgck.ROUTE_REQUEST
+
+
+def P(layout, lens, k, route, max_pkts=4096):
+    return (layout, lens, (("plan_k", k), ("plan_max_pkts", max_pkts), ("plan_route", route)))
+
+
+# family -> how it is reached (cgck_desc_host on pageable or registered memory,
+# cgck_burst_request over a registered mapping's device view)
+SERVER = {
+    "srv_ldsp4": PAGEABLE, "srv_ldsp16": PAGEABLE, "srv_scratch": PAGEABLE, "srv_sys4": REQUEST,
+    "srv_sys16": REQUEST, "srv_inplace": REQUEST, "srv_wide_staged": PAGEABLE, "srv_wide_inplace": REQUEST,
+    "srv_store_host": REGISTERED,
+}
+CELLS.update({
+    "srv_ldsp4": ([P("packed", SMALL, 64, "one/lds/ldsp/g4u1/{ldsp}")], NO_STORE),
+    "srv_ldsp16": ([P("packed", OVER80, 12, "one/lds/ldsp/g16u1/{ldsp}")], NO_STORE),
+    "srv_scratch": ([P("packed", BIG, 16, "one/scratch/staged/g16u1/rt"),
+                     P("scattered", MIX4, 48, "one/scratch/staged/g16u4/rt")], NO_STORE),
+    "srv_sys4": ([P("packed", SMALL, 64, "one/lds/sys/g4u1/{sys}"),
+                  P("scattered", SMALL, 64, "one/lds/sys/g4u1/{sys}")], IN_PLACE),
+    "srv_sys16": ([P("packed", MIX4_20, 16, "one/lds/sys/g16u1/{sys}"),
+                   P("scattered", MIX4_20, 16, "one/lds/sys/g16u1/{sys}")], IN_PLACE),
+    "srv_inplace": ([P("packed", MIX4_20, 48, "one/lds/inplace/g16u4/rt"),
+                     P("scattered", MIX4_20, 48, "one/lds/inplace/g16u4/rt"),
+                     P("packed", LONG, 16, "one/lds/inplace/g16u1/rt"),
+                     P("scattered", LONG, 16, "one/lds/inplace/g16u1/rt")], IN_PLACE),
+    "srv_wide_staged": ([P("packed", SMALL, 128, "wide*/slice/staged/g4u1/rt", 128),
+                         P("packed", MID, 128, "wide*/slice/staged/g16u4/rt", 128),
+                         P("scattered", SMALL, MAX_FRAMES, "wide*/slice/staged/g4u1/rt"),
+                         P("scattered", MID, MAX_FRAMES, "wide*/slice/staged/g16u4/rt")], NO_STORE),
+    "srv_wide_inplace": ([P("scattered", SMALL, 128, "wide*/slice/inplace/g4u1/rt", 128),
+                          P("scattered", MID, 128, "wide*/slice/inplace/g16u4/rt", 128),
+                          P("packed", SMALL, MAX_FRAMES, "wide*/slice/inplace/g4u1/rt"),
+                          P("packed", MID, MAX_FRAMES, "wide*/slice/inplace/g16u4/rt")], IN_PLACE),
+    "srv_store_host": ([P("scattered", SMALL, 64, "one/lds/sys/g4u1/{sys}"),
+                        P("packed", MIX4_20, 16, "one/lds/sys/g16u1/{sys}"),
+                        P("scattered", MIX4_20, 48, "one/lds/inplace/g16u4/rt")],
+                       [f for f in FLAG_SETS if f & cgck.STORE]),
+})
+
+
+def requests(batch, k):
+    """The request plan: consecutive windows (lo, hi) of the batch, as few as hold
+    at most k frames each and of sizes that differ by at most one, so the last
+    request is no smaller than the others and takes their route."""
+    m = -(-batch.n // k)
+    return [(batch.n * i // m, batch.n * (i + 1) // m) for i in range(m)]
+
+
+def plan(cell):
+    """(k, max_pkts, route) of a server cell, the route with fl / rt filled in."""
+    (_, _, kw), flags = cell
+    kw = dict(kw)
+    fl = {"sys": "fl" if flags in COMPILED else "rt", "ldsp": "fl" if flags in COMPILED + (cgck.RAW,) else "rt"}
+    return kw["plan_k"], kw["plan_max_pkts"], kw["plan_route"].format(**fl)
+
+
+def route_of(b, lo, hi, flags, mem, max_pkts, max_bytes=SERVER_BYTES):
+    """The route the library names for frames [lo, hi) of the batch as one request."""
+    return cgck.burst_route(max_pkts, max_bytes, mem, b.lens[lo:hi], flags)
+
+
+def route_kinds(name):
+    """The kinds of body a route name stands for (cgck.burst_route_kinds lists them
+    all): W and the pass count left out, one U a kind."""
+    p = name.split("/")
+    if len(p) < 5:
+        return set()
+    p[0] = "wide" if p[0].startswith("wide") else p[0]
+    g, us = p[3].split("u", 1)
+    kinds = {"/".join(p[:3] + [f"{g}u{u.lstrip('u')}", p[4]]) for u in us.split("+")}
+    if len(p) > 5:
+        kinds.add("/".join(p[:3] + ["passes"]))
+    return kinds
+
+
+# The second slice pass (test_server_slice_passes): one request of PASS_N frames
+# to a server opened for as many.  32 workgroups take 1026 or 1027 frames each:
+# a full pass of 1024 descriptors, then a pass of 2 or 3.
+PASS_N = 32 * 1024 + 71
+PASS_BYTES = 8 << 20           # max_bytes: the mid mix staged is 32839 frames of ~200 padded bytes, 6.4 MB
+PASS_CLASSES = ("zero_ip", "zero_l4", "zero_both", "stored", "hl_sweep", "fill")
+PASS_CELLS = {   # mix -> the corpus cell per flag set
+    "small": (("scattered", SMALL, ()), [G, cgck.VERIFY_BSD, cgck.VERIFY_TOY, cgck.FILL_BOTH]),
+    "mid": (("scattered", MID, ()), [G, cgck.VERIFY_BSD, cgck.VERIFY_TOY]),
+}
+
+
+def second_pass(route, n=PASS_N, per_pass=1024):
+    """The request indices that fall in a second pass of their slice, W taken from
+    the route's name ("wide32/...")."""
+    W = int(route.split("/")[0][4:])
+    return [k for j in range(W) for k in range(n * j // W + per_pass, n * (j + 1) // W)]
+
+
+def pass_batch(b, route, tiled):
+    """PASS_N frames from the batch b: request k is frame (k + rot) % b.n, with
+    the smallest rotation that puts every class b holds of PASS_CLASSES into a
+    second pass.  tiled: copy k // b.n of the buffer holds it, so no two share a
+    byte (CGCK_STORE); else the descriptors overlap in the one buffer."""
+    want = {f.cls for f in b.frames} & set(PASS_CLASSES)
+    late = second_pass(route)
+    rot = next(r for r in range(b.n) if {b.frames[(k + r) % b.n].cls for k in late} >= want)
+    idx = (np.arange(PASS_N) + rot) % b.n
+    tile = (np.arange(PASS_N) // b.n) * len(b.buf) if tiled else 0
+    starts = b.starts[idx] + tile
+    buf = np.tile(b.buf, -(-PASS_N // b.n)) if tiled else b.buf.copy()
+    return Batch(buf, [b.frames[i] for i in idx], _desc(starts, b.desc["l3_off"][idx].astype(np.int64), b.lens[idx]),
+                 starts=starts)
+
+
+# The RX window's frames (test_rx_window_edge_classes): those of frames4, under
+# headers a stack reads on (header4's sane), whose header a stack takes: the
+# zero-sum, planted-field and 0xFF-payload frames and the ip_hl sweep from 5 up
+# to the frame's length, in bursts for the system-coherent G = 16 and G = 4
+# bodies and for slices.
+RX_LENS = (64, 99, 1500)
+RX_L2 = (14, 16, 21)           # q even, zero and odd: the header bytes in chunk 0, chunk 1, across both
+
+
+def rx_frames(port, ln):
+    rng = np.random.default_rng(0x5A00 + ln)
+    return [f for f in frames4(port, rng, ln, cgck.VERIFY_BSD, sane=True)
+            if f.cls.startswith("zero_") or f.cls == "stored" or f.label == "fill:hdr_ff"
+            or (f.cls == "hl_sweep" and 20 <= f.hl * 4 <= ln)]
+
+
+def rx_bursts(port):
+    """[(name, frames)]: bursts of 16 of every length mixed, of 64 frames of 64
+    bytes, and one of 300."""
+    per = [rx_frames(port, ln) for ln in RX_LENS]
+    mixed = [f for i in range(max(map(len, per))) for x in per for f in x[i:i + 1]]
+    small = per[0]
+    return ([(f"16@{i}", mixed[i:i + 16]) for i in range(0, len(mixed) - 15, 16)]
+            + [(f"64@{i}", small[i:i + 64]) for i in range(0, len(small) - 63, 64)] + [("300", mixed[:300])])
+
+
 def cells(family):
     return [(shape, flags) for shape in CELLS[family][0] for flags in CELLS[family][1]]
 
 
+def launched_mixes():
+    """(layout, mix) of the launched families' cells."""
+    return {(layout, lens) for fam, (shapes, _) in CELLS.items() if fam not in SERVER
+            for layout, lens, _ in shapes if not np.isscalar(lens)}
+
+
 def cell_id(cell):
     (layout, lens, kw), flags = cell
-    ln = lens if np.isscalar(lens) else "mix"
+    # (the launched families' mixes keep the plain "mix"; a server family's mix
+    # is named by its count and longest frame, so no two batches share an id)
+    ln = lens if np.isscalar(lens) else "mix" if (layout, lens) in launched_mixes() else f"mix{len(lens)}x{max(lens)}"
+    if dict(kw).get("plan_route"):   # a server cell: its plan, as k<frames a request>-m<max_pkts>
+        kw = [(k, f"{k[5]}{v}") for k, v in kw if k != "plan_route"]
     return f"{layout}-{ln}-{'-'.join(str(v) for _, v in kw)}-{flags:#x}".replace("--", "-")
+
+
+def corpus_cell(cell):
+    """The cell without its request plan: server cells that differ only in the
+    plan share one batch."""
+    (layout, lens, kw), flags = cell
+    return (layout, lens, tuple(x for x in kw if x[0] not in PLAN_KEYS)), flags
 
 
 _cache = {}
@@ -493,7 +680,7 @@ _cache = {}
 
 def cell_batch(port, cell):
     """The batch of a cell (built once a session; callers copy what they change)."""
-    (layout, lens, kw), flags = cell
+    (layout, lens, kw), flags = corpus_cell(cell)
     key = (layout, lens, kw, flags)
     if key not in _cache:
         seed = 0xED6E + sum(ord(c) for c in layout) * 7 + int(np.sum(lens)) * 131 + flags

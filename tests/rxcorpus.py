@@ -120,15 +120,17 @@ def corpus(rng, ck, n, clean=False):
     return out
 
 
-def ring(frames):
-    """(ring bytes, DESC_DTYPE descriptors): frame k in slot k at +L2."""
+def ring(frames, l2=L2):
+    """(ring bytes, DESC_DTYPE descriptors): frame k in slot k at +l2 (the
+    Ethernet header in the 14 bytes before it)."""
+    assert l2 >= L2
     buf = np.zeros(len(frames) * SLOT + 64, np.uint8)
     desc = np.zeros(len(frames), cgck.DESC_DTYPE)
     for k, p in enumerate(frames):
         o = k * SLOT
-        buf[o:o + L2] = (0x02, 0, 0, 0, 0, 1, 0x02, 0, 0, 0, 0, 2, 0x08, 0x00)
-        buf[o + L2:o + L2 + len(p)] = p
-        desc[k] = (o, L2, len(p))
+        buf[o + l2 - L2:o + l2] = (0x02, 0, 0, 0, 0, 1, 0x02, 0, 0, 0, 0, 2, 0x08, 0x00)
+        buf[o + l2:o + l2 + len(p)] = p
+        desc[k] = (o, l2, len(p))
     return buf, desc
 
 

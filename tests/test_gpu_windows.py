@@ -177,20 +177,23 @@ def test_rx_window_threads(port):
 # TX window
 # ---------------------------------------------------------------------------
 
-def tx_calls(row, ln, fo):
-    """tcp_output.c:416-418 then ip_output.c:61-64 on the packet at row+14."""
+def tx_calls(row, ln, fo, icmp=False):
+    """tcp_output.c:416-418 (udp_usrreq.c:186-190 alike) then ip_output.c:61-64
+    on the packet at row+14; icmp: the message's own sum first, by in_cksum
+    without a pseudo-header (ip_icmp.c:68-80)."""
     row[14 + 20 + fo:14 + 20 + fo + 2] = 0
-    v = cgck.udp_cksum(row, 14, ln - 20)
+    v = cgck.in_cksum(row, 14 + 20, ln - 20) if icmp else cgck.udp_cksum(row, 14, ln - 20)
     row[14 + 20 + fo:14 + 20 + fo + 2] = np.frombuffer(np.uint16(v).tobytes(), np.uint8)
     row[14 + 10:14 + 12] = 0
     v = cgck.ip_cksum(row, 14)
     row[14 + 10:14 + 12] = np.frombuffer(np.uint16(v).tobytes(), np.uint8)
 
 
-def expected(port, pkt, fo):
+def expected(port, pkt, fo, icmp=False):
     ref = pkt.copy()
     ref[20 + fo:22 + fo] = 0
-    ref[20 + fo:22 + fo] = np.frombuffer(np.uint16(port.udp_cksum(ref, 0, len(ref) - 20)).tobytes(), np.uint8)
+    v = port.in_cksum(ref, 20, len(ref) - 20) if icmp else port.udp_cksum(ref, 0, len(ref) - 20)
+    ref[20 + fo:22 + fo] = np.frombuffer(np.uint16(v).tobytes(), np.uint8)
     ref[10:12] = 0
     ref[10:12] = np.frombuffer(np.uint16(port.in_cksum(ref, 0, 20)).tobytes(), np.uint8)
     return ref
