@@ -75,6 +75,12 @@ class RssRes(ctypes.Structure):
     _fields_ = [("hash", ctypes.c_void_p), ("kind", ctypes.c_void_p), ("queue", ctypes.c_void_p),
                 ("qcount", ctypes.c_void_p)]
 
+
+class SteerRes(ctypes.Structure):
+    """cgck_steer_res_t: the optional outputs of the partition by queue id."""
+    _fields_ = [("qoff", ctypes.c_void_p), ("perm", ctypes.c_void_p), ("slot", ctypes.c_void_p),
+                ("desc_out", ctypes.c_void_p)]
+
 # Every symbol include/cgck.h declares (checked by tests/test_abi.py).
 EXPORTS = (
     "in_cksum", "udp_cksum", "cgck_last_error", "cgck_abi_version", "cgck_ctx_create",
@@ -95,6 +101,7 @@ EXPORTS = (
     "cgck_synth_imix_ip6", "cgck_synth_imix_ring_ip6", "cgck_synth_imix_dual",
     "cgck_rss_strided", "cgck_rss_desc", "cgck_rss_desc_host",
     "cgck_test_burst_route", "cgck_test_burst_route_kind",
+    "cgck_steer_work_bytes", "cgck_steer", "cgck_rss_steer_desc", "cgck_test_steer_plan",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -182,6 +189,14 @@ def bind(path):
         L.cgck_rss_strided.argtypes = [_vp, _vp, _u64, _u64, _u32, _u32, _spec, _res, _vp]
         L.cgck_rss_desc.argtypes = [_vp, _vp, _vp, _u64, _spec, _res, _vp]
         L.cgck_rss_desc_host.argtypes = [_vp, _vp, ctypes.c_size_t, _vp, _u64, _spec, _res]
+    if hasattr(L, "cgck_steer"):               # the partition by queue id (an older build loads without it)
+        _spec, _res, _sres = ctypes.POINTER(RssSpec), ctypes.POINTER(RssRes), ctypes.POINTER(SteerRes)
+        L.cgck_steer_work_bytes.restype = ctypes.c_size_t
+        L.cgck_steer_work_bytes.argtypes = [_u64, _u32]
+        L.cgck_steer.argtypes = [_vp, _vp, _u64, _u32, _vp, _sres, _vp, _vp]
+        L.cgck_rss_steer_desc.argtypes = [_vp, _vp, _vp, _u64, _spec, _res, _sres, _vp, _vp]
+        L.cgck_test_steer_plan.argtypes = [_u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
+                                           ctypes.POINTER(ctypes.c_size_t)]
     L.cgck_dst_cache.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32, _vp, _vp]
     L.cgck_dst_cache_host.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32,
                                       ctypes.POINTER(_u32)]
@@ -304,6 +319,22 @@ def burst_route_kinds():
         kinds[buf.value.decode()] = bool(rc)
         i += 1
     return kinds
+
+
+def steer_plan(n, queue_num):
+    """cgck_test_steer_plan: (tile, tiles, work_bytes) of cgck_steer over n frames
+    and queue_num queues.  Needs no device."""
+    tile, tiles, work = _u32(), _u32(), ctypes.c_size_t()
+    rc = load().cgck_test_steer_plan(n, queue_num, ctypes.byref(tile), ctypes.byref(tiles), ctypes.byref(work))
+    if rc < 0:
+        raise CgckError(f"cgck_test_steer_plan failed ({rc})")
+    return tile.value, tiles.value, work.value
+
+
+def steer_work_bytes(n, queue_num):
+    """cgck_steer_work_bytes: the workspace cgck_steer needs (0: none, one tile).
+    Needs no device."""
+    return load().cgck_steer_work_bytes(n, queue_num)
 
 
 def last_error():
@@ -635,6 +666,23 @@ class Engine:
         res = RssRes(*(None if a is None else a.ctypes.data for a in (hash, kind, queue, qcount)))
         _check(load().cgck_rss_desc_host(self.ctx, base.ctypes.data, base.nbytes, desc.ctypes.data, len(desc),
                                          ctypes.byref(spec), ctypes.byref(res)), "cgck_rss_desc_host")
+
+    def steer(self, queue, n, queue_num, desc_in=None, qoff=None, perm=None, slot=None, desc_out=None,
+              work=None, stream=None):
+        """cgck_steer: the stable partition of n frames by their queue bytes; device
+        pointers or None (work: at least steer_work_bytes(n, queue_num) bytes).
+        Asynchronous."""
+        res = SteerRes(qoff, perm, slot, desc_out)
+        _check(load().cgck_steer(self.ctx, queue, n, queue_num, desc_in, ctypes.byref(res), work, stream),
+               "cgck_steer")
+
+    def rss_steer_desc(self, base, desc, n, spec, queue, hash=None, kind=None, qcount=None, qoff=None,
+                       perm=None, slot=None, desc_out=None, work=None, stream=None):
+        """cgck_rss_steer_desc: rss_desc into `queue` (required), then steer over
+        it with spec.queue_num queues, on one stream.  Asynchronous."""
+        rss, res = RssRes(hash, kind, queue, qcount), SteerRes(qoff, perm, slot, desc_out)
+        _check(load().cgck_rss_steer_desc(self.ctx, base, desc, n, ctypes.byref(spec), ctypes.byref(rss),
+                                          ctypes.byref(res), work, stream), "cgck_rss_steer_desc")
 
     @staticmethod
     def dst_params(laddr, faddr, fport, queue_num, queue_id, key=None, key_size=None):

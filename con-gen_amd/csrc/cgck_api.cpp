@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "cgck_host.h"
+#include "cgck_steer_plan.h"
 
 using namespace cgck;
 
@@ -1909,6 +1910,91 @@ extern "C" int cgck_rss_desc_host(cgck_ctx_t *c, const void *base, size_t bytes,
 	for (uint32_t q = 0; res->qcount && q < qn; q++)
 		res->qcount[q] += c->h_out[q];
 	return 0;
+}
+
+// Stable partition by queue id (cgck_steer.hip).  The argument rules cgck_steer
+// and cgck_rss_steer_desc share; `what` names the caller in the message.
+static int steer_check(const char *what, const cgck_ctx *c, const uint8_t *queue, uint64_t n, uint32_t queue_num,
+		       const cgck_desc_t *desc_in, const cgck_steer_res_t *res, const void *work)
+{
+	if (!c || !queue || !res)
+		return set_err(-EINVAL, "%s: NULL context, queue or res", what);
+	if (!res->qoff && !res->perm && !res->slot && !res->desc_out)
+		return set_err(-EINVAL, "%s: every output is NULL", what);
+	if (queue_num == 0 || queue_num > kSteerMaxQueues)
+		return set_err(-EINVAL, "%s: queue_num %u outside 1..128 (RSS_QUEUE_ID_MAX)", what, queue_num);
+	if (n > 0xFFFFFFFFull)
+		return set_err(-EINVAL, "%s: n %llu above 0xFFFFFFFF", what, (unsigned long long)n);
+	if (res->desc_out && !desc_in)
+		return set_err(-EINVAL, "%s: desc_out given without desc_in", what);
+	if (res->desc_out && res->desc_out == desc_in)
+		return set_err(-EINVAL, "%s: desc_out must not be desc_in", what);
+	if (((uintptr_t)desc_in & 3) != 0 || ((uintptr_t)res->desc_out & 3) != 0)
+		return set_err(-EINVAL, "%s: descriptors must be 4-byte aligned", what);
+	if (!work && steer_plan(n, queue_num).work_bytes != 0)
+		return set_err(-EINVAL, "%s: NULL work for %llu frames (cgck_steer_work_bytes)", what,
+			       (unsigned long long)n);
+	if (((uintptr_t)work & 3) != 0)
+		return set_err(-EINVAL, "%s: work must be 4-byte aligned", what);
+	return 0;
+}
+
+static int steer_run(cgck_ctx *c, const uint8_t *queue, uint64_t n, uint32_t queue_num, const cgck_desc_t *desc_in,
+		     const cgck_steer_res_t *res, void *work, hipStream_t st)
+{
+	const SteerPlan plan = steer_plan(n, queue_num);
+	SteerParams p = {};
+	p.queue = queue;
+	p.n = n;
+	p.queue_num = queue_num;
+	p.tile = plan.tile;
+	p.tiles = plan.tiles;
+	p.desc_in = desc_in;
+	p.qoff = res->qoff;
+	p.perm = res->perm;
+	p.slot = res->slot;
+	p.desc_out = res->desc_out;
+	p.hist = (uint32_t *)work;
+	HIP_TRY(launch_steer(p, st));
+	c->last_kernel = t_kernel;
+	return 0;
+}
+
+extern "C" int cgck_steer(cgck_ctx_t *c, const uint8_t *queue, uint64_t n, uint32_t queue_num,
+			  const cgck_desc_t *desc_in, const cgck_steer_res_t *res, void *work, void *stream)
+{
+	int rc = steer_check("cgck_steer", c, queue, n, queue_num, desc_in, res, work);
+	if (rc)
+		return rc;
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	return steer_run(c, queue, n, queue_num, desc_in, res, work, pick(c, stream));
+}
+
+// cgck_rss_desc, then cgck_steer over the queue ids it wrote, on one stream.
+extern "C" int cgck_rss_steer_desc(cgck_ctx_t *c, const void *base, const cgck_desc_t *desc, uint64_t n,
+				   const cgck_rss_spec_t *spec, const cgck_rss_res_t *rss, const cgck_steer_res_t *res,
+				   void *work, void *stream)
+{
+	int rc = rss_frames_check("cgck_rss_steer_desc", c, base, desc, true, n, spec, rss);
+	if (rc)
+		return rc;
+	if (!rss->queue)
+		return set_err(-EINVAL, "cgck_rss_steer_desc: rss->queue is NULL (the steer's input)");
+	if ((rc = steer_check("cgck_rss_steer_desc", c, rss->queue, n, spec->queue_num, desc, res, work)))
+		return rc;
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = pick(c, stream);
+	RssfParams p = {};
+	p.base = (const uint8_t *)base;
+	p.desc = desc;
+	p.n = n;
+	if ((rc = rss_frames_run(c, p, spec, rss, st)))
+		return rc;
+	return steer_run(c, rss->queue, n, spec->queue_num, desc, res, work, st);
 }
 
 extern "C" int cgck_dst_cache(cgck_ctx_t *c, const cgck_dst_params_t *prm, cgck_dst_entry_t *out, uint32_t cap,

@@ -172,7 +172,27 @@ struct RssfParams {
 	uint32_t *qcount;
 };
 
+// Stable partition of a burst by queue id (cgck_steer.hip; include/cgck.h,
+// section 3).  tile and tiles are steer_plan()'s (cgck_steer_plan.h); hist is the
+// caller's workspace, u32[queue_num + 1][tiles], unused with one tile; nbits
+// (the bits of a bin) and per_wave (frames per wave of a tile) are set by
+// launch_steer.
+struct SteerParams {
+	const uint8_t *queue;
+	uint64_t n;
+	uint32_t queue_num;
+	uint32_t tile, tiles;
+	uint32_t nbits, per_wave;
+	const void *desc_in;
+	uint32_t *qoff;
+	uint32_t *perm;
+	uint32_t *slot;
+	void *desc_out;
+	uint32_t *hist;
+};
+
 hipError_t launch_rssf(const RssfParams &p, int num_cus, hipStream_t st);
+hipError_t launch_steer(const SteerParams &p, hipStream_t st);
 hipError_t launch_toeplitz(const RssParams &p, int num_cus, hipStream_t st);
 hipError_t launch_dst_cache(const DstParams &p, int num_cus, hipStream_t st);
 uint32_t dst_iters(uint32_t n, uint32_t cap, bool filter, uint64_t pass_lo, uint64_t pass_hi, int num_cus);

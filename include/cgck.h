@@ -589,6 +589,76 @@ int cgck_rss_desc(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *desc, ui
 int cgck_rss_desc_host(cgck_ctx_t *ctx, const void *base, size_t bytes, const cgck_desc_t *desc, uint64_t n,
 		       const cgck_rss_spec_t *spec, const cgck_rss_res_t *res);
 
+/* Software steer: a stable counting partition of a device-resident burst by
+ * queue id, the step from cgck_rss_desc's one byte per frame to "worker q
+ * verifies queue q's frames" without a host pass (INTEGRATION.md has the
+ * recipe; DESIGN.md §5.10 the kernels and the measurements).
+ *
+ * Bins.   bin(k) = queue[k] when queue[k] < queue_num, else queue_num: that last
+ *         bin is the unsteered bucket, which takes the 0xFF of a frame without a
+ *         hash and any other byte not below queue_num.  The call is total over
+ *         all 256 byte values: no input byte makes it fail on the device.
+ * Order.  Slots are filled by ascending bin and, within a bin, by ascending
+ *         arrival index k: the partition is stable (a flow's frames keep their
+ *         order) and the output is fully determined.
+ * qoff    qoff[q] = the first slot of bin q, q in 0..queue_num (qoff[queue_num]:
+ *         the first unsteered slot); qoff[queue_num + 1] = n.  Written, not
+ *         accumulated.
+ * perm    perm[s] = the arrival index k of the frame in slot s.
+ * slot    slot[k] = s, the inverse of perm (carries per-slot results back to
+ *         arrival order).
+ * desc_out  desc_out[s] = desc_in[perm[s]]: queue q's descriptors are
+ *         desc_out[qoff[q] .. qoff[q + 1]).
+ * Arguments.  queue_num is 1..128, as in cgck_rss_spec_t; n <= 0xFFFFFFFF.
+ *         desc_in may be NULL when desc_out is NULL (a strided caller uses perm).
+ *         desc_in and desc_out are 4-byte aligned, as for CGCK_MIXED, and must
+ *         not be the same array.
+ * Workspace.  `work` is caller-owned device memory of at least
+ *         cgck_steer_work_bytes(n, queue_num) bytes, 4-byte aligned.  It need not
+ *         be zeroed and holds nothing between calls.  The library keeps no hidden
+ *         scratch for this call: two calls in flight on two streams of one context
+ *         are independent (unlike the table cache).  cgck_steer_work_bytes is pure
+ *         (no device, no context) and returns 0 for every n that fits one tile (n
+ *         <= 4096 frames: any receive burst), and `work` may then be NULL.
+ * Execution.  Asynchronous on `stream` (NULL: the context's).  n == 0 returns 0,
+ *         launches nothing and writes nothing (cgck_rss_desc's rule).  The inputs
+ *         (queue, desc_in, the frames) are never written.  One tile takes one
+ *         launch (steer_one_kernel); more take three (count, scan, scatter), and
+ *         no workgroup ever waits for another.
+ * Measured (DESIGN.md §5.10, 16M dual-stack IMIX frames on one MI355X): all four
+ *         outputs take 0.27 ms with 8 queues and 0.55 ms with 128, against 0.48 ms
+ *         for the cgck_rss_desc that feeds them and 210 / 920 ms for the host
+ *         route (queue[] down, a stable numpy bucket, the descriptors up); perm
+ *         alone takes 0.09 / 0.27 ms.  On a burst the one launch takes 6 us at 256
+ *         frames and 17 us at 4096, the three launches 11 and 22 us: keep device
+ *         bursts within one tile.
+ * There is no host form: a host burst's queue[] already lies on the host after
+ * cgck_rss_desc_host, and a bucket loop over a few hundred bytes there costs less
+ * than one launch.
+ * -EINVAL: a NULL ctx, queue or res; every output NULL; queue_num 0 or above
+ * 128; n above 0xFFFFFFFF; desc_out without desc_in; desc_out == desc_in; a
+ * misaligned descriptor array or workspace; work NULL while
+ * cgck_steer_work_bytes(n, queue_num) != 0. */
+typedef struct cgck_steer_res { /* device memory; each optional (NULL); at least one non-NULL */
+	uint32_t *qoff;        /* u32[queue_num + 2], written (not accumulated) */
+	uint32_t *perm;        /* u32[n]: perm[s] = arrival index k of the frame in slot s */
+	uint32_t *slot;        /* u32[n]: slot[k] = s, the inverse of perm */
+	cgck_desc_t *desc_out; /* cgck_desc_t[n]: desc_out[s] = desc_in[perm[s]] */
+} cgck_steer_res_t;
+
+size_t cgck_steer_work_bytes(uint64_t n, uint32_t queue_num);
+int cgck_steer(cgck_ctx_t *ctx, const uint8_t *queue, uint64_t n, uint32_t queue_num,
+	       const cgck_desc_t *desc_in, const cgck_steer_res_t *res, void *work, void *stream);
+/* Hash and steer: cgck_rss_desc with `spec` and `rss`, then cgck_steer over
+ * rss->queue with queue_num = spec->queue_num and desc_in = desc, on one stream.
+ * rss->queue is required (it is the steer's input; the library allocates none)
+ * and so is spec->queue_num >= 1; rss's other arrays stay optional, and qcount
+ * keeps its running-counter meaning.  -EINVAL: cgck_rss_desc's list, cgck_steer's
+ * list, a NULL rss->queue, queue_num 0. */
+int cgck_rss_steer_desc(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *desc, uint64_t n,
+			const cgck_rss_spec_t *spec, const cgck_rss_res_t *rss, const cgck_steer_res_t *res,
+			void *work, void *stream);
+
 /* One dst-cache entry: the fields thread_init_dst_cache fills in struct
  * ip_socket (con-gen.c:344-349; subr.h:218-228).  16 bytes. */
 typedef struct cgck_dst_entry {
@@ -677,6 +747,12 @@ int cgck_test_burst_stale(cgck_ctx_t *ctx, uint32_t from);
 int cgck_test_burst_route(uint32_t max_pkts, size_t max_bytes, int mem, int posted, uint64_t n, uint32_t max_len,
                           uint64_t pkt_bytes, uint32_t flags, uint32_t n1, char *name, size_t cap);
 int cgck_test_burst_route_kind(uint32_t i, char *kind, size_t cap);
+/* The geometry cgck_steer uses for (n, queue_num): frames per tile (a multiple of
+ * 256, doubling from 4096 so that tiles x (queue_num + 1) stays within 262144
+ * words), tiles = ceil(n / tile), and cgck_steer_work_bytes' value.  Each output
+ * pointer may be NULL.  Needs no device and no context.  -EINVAL: queue_num
+ * outside 1..128 or n above 0xFFFFFFFF. */
+int cgck_test_steer_plan(uint64_t n, uint32_t queue_num, uint32_t *tile, uint32_t *tiles, size_t *work_bytes);
 
 #ifdef __cplusplus
 }
