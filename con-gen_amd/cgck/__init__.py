@@ -76,6 +76,22 @@ class RssRes(ctypes.Structure):
                 ("qcount", ctypes.c_void_p)]
 
 
+# cgck_l2_desc: the class in the low nibble of cls[k], the flag bits beside it,
+# and the length of the counter array.
+L2_IP4, L2_IP6, L2_ARP, L2_OTHER, L2_RUNT = 0, 1, 2, 3, 4
+L2_TOOSMALL, L2_BADVERS, L2_BADHLEN, L2_BADLEN, L2_TOOSHORT = 5, 6, 7, 8, 9
+L2_NCLASS = 10
+L2_VLAN = 1 << 4
+L2_BCAST = 1 << 6
+L2_MCAST = 1 << 7
+L2_NCOUNT = 12          # [class] for the ten classes, [10] BCAST or MCAST frames, [11] tagged frames
+
+
+class L2Res(ctypes.Structure):
+    """cgck_l2_res_t: the optional outputs of the raw-burst classifier."""
+    _fields_ = [("desc_out", ctypes.c_void_p), ("cls", ctypes.c_void_p), ("count", ctypes.c_void_p)]
+
+
 class SteerRes(ctypes.Structure):
     """cgck_steer_res_t: the optional outputs of the partition by queue id."""
     _fields_ = [("qoff", ctypes.c_void_p), ("perm", ctypes.c_void_p), ("slot", ctypes.c_void_p),
@@ -102,6 +118,7 @@ EXPORTS = (
     "cgck_rss_strided", "cgck_rss_desc", "cgck_rss_desc_host",
     "cgck_test_burst_route", "cgck_test_burst_route_kind",
     "cgck_steer_work_bytes", "cgck_steer", "cgck_rss_steer_desc", "cgck_test_steer_plan",
+    "cgck_l2_desc", "cgck_synth_eth", "cgck_test_l2_pass",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -197,6 +214,10 @@ def bind(path):
         L.cgck_rss_steer_desc.argtypes = [_vp, _vp, _vp, _u64, _spec, _res, _sres, _vp, _vp]
         L.cgck_test_steer_plan.argtypes = [_u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
                                            ctypes.POINTER(ctypes.c_size_t)]
+    if hasattr(L, "cgck_l2_desc"):             # the raw-burst classifier (an older build loads without it)
+        L.cgck_l2_desc.argtypes = [_vp, _vp, _vp, _u64, ctypes.POINTER(L2Res), _vp]
+        L.cgck_synth_eth.argtypes = [_vp, _vp, _vp, _vp, _u64, _u32, _u64, _vp]
+        L.cgck_test_l2_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.cgck_dst_cache.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32, _vp, _vp]
     L.cgck_dst_cache_host.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32,
                                       ctypes.POINTER(_u32)]
@@ -683,6 +704,25 @@ class Engine:
         rss, res = RssRes(hash, kind, queue, qcount), SteerRes(qoff, perm, slot, desc_out)
         _check(load().cgck_rss_steer_desc(self.ctx, base, desc, n, ctypes.byref(spec), ctypes.byref(rss),
                                           ctypes.byref(res), work, stream), "cgck_rss_steer_desc")
+
+    def l2_desc(self, base, raw, n, desc_out=None, cls=None, count=None, stream=None):
+        """cgck_l2_desc: classify n raw Ethernet frames (raw: {frame_off, offset of
+        the Ethernet header, bytes delivered}) and write the trimmed descriptors,
+        the class bytes and / or the running counters; device pointers or None.
+        Asynchronous."""
+        res = L2Res(desc_out, cls, count)
+        _check(load().cgck_l2_desc(self.ctx, base, raw, n, ctypes.byref(res), stream), "cgck_l2_desc")
+
+    def l2_pass_frames(self):
+        """cgck_test_l2_pass: frames one pass of l2d_kernel's grid covers on this device."""
+        f = _u64()
+        _check(load().cgck_test_l2_pass(self.ctx, ctypes.byref(f)), "cgck_test_l2_pass")
+        return f.value
+
+    def synth_eth(self, base, desc, raw, n, vlan_every, seed, stream=None):
+        """cgck_synth_eth: Ethernet headers (a VLAN tag on every vlan_every-th frame)
+        in front of a ring set's IP headers, and the transport's descriptors in raw."""
+        _check(load().cgck_synth_eth(self.ctx, base, desc, raw, n, vlan_every, seed, stream), "cgck_synth_eth")
 
     @staticmethod
     def dst_params(laddr, faddr, fport, queue_num, queue_id, key=None, key_size=None):

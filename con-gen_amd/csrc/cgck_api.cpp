@@ -1997,6 +1997,44 @@ extern "C" int cgck_rss_steer_desc(cgck_ctx_t *c, const void *base, const cgck_d
 	return steer_run(c, rss->queue, n, spec->queue_num, desc, res, work, st);
 }
 
+// Classify and trim a raw Ethernet burst (cgck_l2d.hip): one launch, no scratch.
+extern "C" int cgck_l2_desc(cgck_ctx_t *c, const void *base, const cgck_desc_t *raw, uint64_t n,
+			    const cgck_l2_res_t *res, void *stream)
+{
+	if (!c || !res || !base)
+		return set_err(-EINVAL, "cgck_l2_desc: NULL context, res or base");
+	if (n && !raw)
+		return set_err(-EINVAL, "cgck_l2_desc: NULL descriptors");
+	if (!res->desc_out && !res->cls && !res->count)
+		return set_err(-EINVAL, "cgck_l2_desc: every output is NULL");
+	if (((uintptr_t)raw & 3) != 0 || ((uintptr_t)res->desc_out & 3) != 0)
+		return set_err(-EINVAL, "cgck_l2_desc: descriptors must be 4-byte aligned");
+	if (res->desc_out && res->desc_out == raw)
+		return set_err(-EINVAL, "cgck_l2_desc: desc_out must not be raw");
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	L2dParams p = {};
+	p.base = (const uint8_t *)base;
+	p.raw = raw;
+	p.n = n;
+	p.zero = c->d_zero;
+	p.desc_out = res->desc_out;
+	p.cls = res->cls;
+	p.count = res->count;
+	HIP_TRY(launch_l2d(p, c->num_cus, pick(c, stream)));
+	c->last_kernel = t_kernel;
+	return 0;
+}
+
+extern "C" int cgck_test_l2_pass(cgck_ctx_t *c, uint64_t *frames)
+{
+	if (!c || !frames)
+		return set_err(-EINVAL, "cgck_test_l2_pass: NULL argument");
+	*frames = l2d_pass_frames(c->num_cus);
+	return 0;
+}
+
 extern "C" int cgck_dst_cache(cgck_ctx_t *c, const cgck_dst_params_t *prm, cgck_dst_entry_t *out, uint32_t cap,
 			      uint32_t *count, void *stream)
 {
@@ -2209,6 +2247,33 @@ extern "C" int cgck_synth_imix_dual(cgck_ctx_t *c, void *base, cgck_desc_t *desc
 	hipStream_t st = pick(c, stream);
 	HIP_TRY(launch_synth_fill((uint8_t *)base, stride ? n * stride : cgck_imix_bytes(n), seed, c->num_cus, st));
 	HIP_TRY(launch_synth_dual((uint8_t *)base, (uint32_t *)desc, n, stride, l3_off, c->num_cus, st));
+	return 0;
+}
+
+extern "C" int cgck_synth_eth(cgck_ctx_t *c, void *base, const cgck_desc_t *desc, cgck_desc_t *raw, uint64_t n,
+			      uint32_t vlan_every, uint64_t seed, void *stream)
+{
+	if (!c || (n && (!base || !desc || !raw)))
+		return set_err(-EINVAL, "cgck_synth_eth: bad arguments");
+	if (((uintptr_t)desc & 3) || ((uintptr_t)raw & 3))
+		return set_err(-EINVAL, "cgck_synth_eth: misaligned descriptors");
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = pick(c, stream);
+	// no frame is written before every l3_off is known to leave room
+	int rc = grow_dev((void **)&c->d_dst, &c->d_dst_cap, 16);
+	if (rc)
+		return rc;
+	uint32_t flag = 0;
+	HIP_TRY(hipMemsetAsync(c->d_dst, 0, 4, st));
+	HIP_TRY(launch_synth_eth_check((const uint32_t *)desc, n, (uint32_t *)c->d_dst, c->num_cus, st));
+	HIP_TRY(hipMemcpyAsync(&flag, c->d_dst, 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(CGCK_SYNC(st));
+	if (flag)
+		return set_err(-EINVAL, "cgck_synth_eth: an l3_off below 18 leaves no room for the header and a tag");
+	HIP_TRY(launch_synth_eth((uint8_t *)base, (const uint32_t *)desc, (uint32_t *)raw, n, vlan_every, seed, c->num_cus,
+				 st));
 	return 0;
 }
 

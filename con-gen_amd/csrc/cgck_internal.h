@@ -191,6 +191,22 @@ struct SteerParams {
 	uint32_t *hist;
 };
 
+// Classify and trim a raw Ethernet burst (cgck_l2d.hip; include/cgck.h, section
+// 3).  raw: the transport's descriptors; `zero` = the context's zero chunk; each
+// output may be nullptr.
+struct L2dParams {
+	const uint8_t *base;
+	const void *raw;
+	uint64_t n;
+	const void *zero;
+	void *desc_out;
+	uint8_t *cls;
+	uint32_t *count;
+};
+
+// Workgroups one launch of l2d_kernel runs at most, and frames they cover per pass.
+uint64_t l2d_pass_frames(int num_cus);
+hipError_t launch_l2d(const L2dParams &p, int num_cus, hipStream_t st);
 hipError_t launch_rssf(const RssfParams &p, int num_cus, hipStream_t st);
 hipError_t launch_steer(const SteerParams &p, hipStream_t st);
 hipError_t launch_toeplitz(const RssParams &p, int num_cus, hipStream_t st);
@@ -224,5 +240,9 @@ hipError_t launch_synth_imix6(uint8_t *base, uint32_t *desc, uint64_t n, uint64_
 			      uint32_t nh, int num_cus, hipStream_t st);
 hipError_t launch_synth_dual(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t stride, uint32_t l3_off, int num_cus,
 			     hipStream_t st);
+// cgck_synth_eth: flag |= 1 when a descriptor's l3_off is below 18; then the framing.
+hipError_t launch_synth_eth_check(const uint32_t *desc, uint64_t n, uint32_t *flag, int num_cus, hipStream_t st);
+hipError_t launch_synth_eth(uint8_t *base, const uint32_t *desc, uint32_t *raw, uint64_t n, uint32_t vlan_every,
+			    uint64_t seed, int num_cus, hipStream_t st);
 
 } // namespace cgck

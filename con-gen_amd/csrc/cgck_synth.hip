@@ -232,6 +232,71 @@ hipError_t launch_synth_dual(uint8_t *base, uint32_t *desc, uint64_t n, uint64_t
 	return hipGetLastError();
 }
 
+// cgck_synth_eth: Ethernet framing in front of a ring set's IP headers, and the
+// transport's descriptors {frame_off, l3_off - h, max(ip_len + h, 60)}.
+__global__ __launch_bounds__(256) void synth_eth_check_kernel(const uint32_t *desc, uint64_t n, uint32_t *flag)
+{
+	bool bad = false;
+	for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (uint64_t)gridDim.x * 256)
+		bad |= (desc[3 * k + 2] & 0xffffu) < 18;
+	if (bad)
+		atomicOr(flag, 1u);
+}
+
+__global__ __launch_bounds__(256) void synth_eth_kernel(uint8_t *base, const uint32_t *desc, uint32_t *raw, uint64_t n,
+							uint32_t vlan_every, uint64_t seed)
+{
+	for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (uint64_t)gridDim.x * 256) {
+		const uint32_t lo = desc[3 * k + 0], hi = desc[3 * k + 1], w2 = desc[3 * k + 2];
+		const uint32_t l3 = w2 & 0xffffu, len = w2 >> 16;
+		const bool t = vlan_every && k % vlan_every == 0;
+		const uint32_t h = t ? 18 : 14;
+		uint8_t *ip = base + (((uint64_t)hi << 32) | lo) + l3;
+		uint8_t *e = ip - h;
+		const uint64_t m0 = splitmix64(seed, 2 * k), m1 = splitmix64(seed, 2 * k + 1);
+		for (int i = 0; i < 8; ++i)
+			e[i] = (uint8_t)(m0 >> (8 * i));
+		for (int i = 0; i < 4; ++i)
+			e[8 + i] = (uint8_t)(m1 >> (8 * i));
+		e[0] &= 0xfe;
+		if (t) {
+			e[12] = 0x81;
+			e[13] = 0x00;
+			e[14] = (uint8_t)((k >> 8) & 0x0f);
+			e[15] = (uint8_t)k;
+		}
+		const uint32_t v = ip[0] >> 4;
+		const uint32_t et = v == 4 ? 0x0800u : v == 6 ? 0x86DDu : 0x0806u;
+		e[h - 2] = (uint8_t)(et >> 8);
+		e[h - 1] = (uint8_t)et;
+		const uint32_t L = len + h < 60 ? 60 : len + h > 65535 ? 65535 : len + h;
+		raw[3 * k + 0] = lo;
+		raw[3 * k + 1] = hi;
+		raw[3 * k + 2] = (L << 16) | (l3 - h);
+	}
+}
+
+hipError_t launch_synth_eth_check(const uint32_t *desc, uint64_t n, uint32_t *flag, int num_cus, hipStream_t st)
+{
+	uint64_t want = (n + 255) / 256;
+	int blocks = (int)(want < (uint64_t)num_cus * 8 ? want : (uint64_t)num_cus * 8);
+	if (blocks < 1)
+		blocks = 1;
+	hipLaunchKernelGGL(synth_eth_check_kernel, dim3(blocks), dim3(256), 0, st, desc, n, flag);
+	return hipGetLastError();
+}
+
+hipError_t launch_synth_eth(uint8_t *base, const uint32_t *desc, uint32_t *raw, uint64_t n, uint32_t vlan_every,
+			    uint64_t seed, int num_cus, hipStream_t st)
+{
+	uint64_t want = (n + 255) / 256;
+	int blocks = (int)(want < (uint64_t)num_cus * 8 ? want : (uint64_t)num_cus * 8);
+	if (blocks < 1)
+		blocks = 1;
+	hipLaunchKernelGGL(synth_eth_kernel, dim3(blocks), dim3(256), 0, st, base, desc, raw, n, vlan_every, seed);
+	return hipGetLastError();
+}
+
 hipError_t launch_synth_fill(uint8_t *base, uint64_t nbytes, uint64_t seed, int num_cus, hipStream_t st)
 {
 	uint64_t want = (nbytes / 16 + 255) / 256;

@@ -488,6 +488,22 @@ int cgck_synth_imix_ring_ip6(cgck_ctx_t *ctx, void *base, cgck_desc_t *desc, uin
  * for IPv6); that protocol's checksum field is zeroed when the frame holds it. */
 int cgck_synth_imix_dual(cgck_ctx_t *ctx, void *base, cgck_desc_t *desc, uint64_t n, uint64_t stride,
 			 uint32_t l3_off, uint64_t seed, void *stream);
+/* Ethernet framing for the ring form (stride != 0) of a cgck_synth_imix* set, for
+ * cgck_l2_desc: `desc` is the set's descriptor array, `raw` receives the
+ * transport's view.  For frame k, t = (vlan_every && k % vlan_every == 0) ? 1 : 0
+ * and h = 14 + 4t; the h bytes before the IP header, at frame_off + l3_off - h,
+ * become: twelve address bytes from splitmix64(seed, 2k) and splitmix64(seed, 2k +
+ * 1) (eight and four, low byte first) with bit 0 of byte 0 cleared; when t, TPID
+ * 0x8100 and TCI k & 0x0FFF; the ethertype by the version nibble at l3_off (4:
+ * 0x0800, 6: 0x86DD, anything else 0x0806).  raw[k] = {frame_off, l3_off - h,
+ * max(ip_len + h, 60)}: the padding of a short frame is the ring's own stream
+ * bytes after the packet (non-zero garbage).  The slots must hold l3_off + 1500
+ * bytes, as for cgck_synth_imix_dual.  -EINVAL: a NULL or misaligned argument, or
+ * any l3_off < 18 (no room for the header and a tag); that is checked on the
+ * device before anything is written, so the call waits for `stream` once, and it
+ * uses the context's dst-cache scratch (one such call at a time per context). */
+int cgck_synth_eth(cgck_ctx_t *ctx, void *base, const cgck_desc_t *desc, cgck_desc_t *raw,
+		   uint64_t n, uint32_t vlan_every, uint64_t seed, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* 3. Toeplitz RSS hash (subr.c:482-530, subr.h:370-371) */
@@ -659,6 +675,93 @@ int cgck_rss_steer_desc(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *de
 			const cgck_rss_spec_t *spec, const cgck_rss_res_t *rss, const cgck_steer_res_t *res,
 			void *work, void *stream);
 
+/* Classify and trim a raw Ethernet burst: the stage before every call above.
+ * Those calls start from a cgck_desc_t that already names l3_off and ip_len; a
+ * transport knows only where a frame starts and how many bytes the NIC
+ * delivered.  cgck_l2_desc is ether_input's demultiplex (bsd44/if_ether.c:152-183)
+ * and ip_input's length rules (ip_input.c:28-44, 63-79) as one kernel over a
+ * device-resident burst: it finds the IP header behind up to two VLAN tags, names
+ * the frame's class, and cuts Ethernet padding off by the header's own length
+ * field.  (A 40-byte TCP ACK arrives in a 60-byte frame; with ip_len = 60 - 14 the
+ * pseudo-header length is wrong and a good segment verifies as CGCK_BAD_L4.)
+ *
+ * Input.  raw[k] is a cgck_desc_t read as: frame_off as usual; l3_off the offset
+ * of the Ethernet header inside the slot (0 for most rings); ip_len the bytes
+ * delivered from that offset, L below.  `raw` is any 4-byte aligned array.
+ *
+ * Contract.  With e the L bytes at base + frame_off + l3_off, for every frame:
+ *  1. L < 14: class RUNT.
+ *  2. et = e[12] << 8 | e[13], off = 14, tags = 0.  While et is 0x8100 or 0x88A8
+ *     and tags < 2: if L < off + 4 the class is RUNT (and the walk ends);
+ *     otherwise et = e[off+2] << 8 | e[off+3], off += 4, ++tags.  tags > 0 when the
+ *     walk ends sets CGCK_L2_VLAN, whatever the class.  An et that is still one of
+ *     the two TPIDs after two tags: class OTHER.
+ *  3. Flags, on every frame with L >= 14, whatever its class (if_ether.c:163-168):
+ *     CGCK_L2_BCAST when e[0..5] are all 0xFF, otherwise CGCK_L2_MCAST when
+ *     e[0] & 1.
+ *  4. avail = L - off; b = the bytes from off on.
+ *  5. et == 0x0800, in ip_input's order: avail < 20: TOOSMALL.  b[0] >> 4 != 4:
+ *     BADVERS.  hl = (b[0] & 15) * 4; hl < 20 or hl > avail: BADHLEN.  total =
+ *     b[2] << 8 | b[3]; total < hl: BADLEN.  avail < total: TOOSHORT.  Otherwise
+ *     IP4 with ip_len_out = total.
+ *  6. et == 0x86DD: avail < 40: TOOSMALL.  b[0] >> 4 != 6: BADVERS.  total = 40 +
+ *     (b[4] << 8 | b[5]); avail < total: TOOSHORT.  Otherwise IP6 with ip_len_out
+ *     = total.  There is no jumbogram rule: a jumbogram carries payload length 0
+ *     and comes out as IP6 with ip_len_out = 40 (its fixed header, and a
+ *     Hop-by-Hop header cut off: CGCK_BAD_LEN to every later call); L is 16 bits,
+ *     so a total above 65535 is always TOOSHORT.
+ *  7. et == 0x0806: ARP.  Any other et, an 802.3 length field included: OTHER.
+ *  8. raw.l3_off + off > 65535 (the output field has 16 bits), for a frame that
+ *     rules 1-2 did not already make a RUNT: class RUNT, flags as above.
+ * The result is fully determined for every byte string.
+ *
+ * Outputs.  desc_out[k].frame_off = raw[k].frame_off, always.  IP4 / IP6: l3_off =
+ * raw.l3_off + off, ip_len = ip_len_out.  ARP / OTHER and the drop classes 5-9:
+ * l3_off = raw.l3_off + off, ip_len = 0.  RUNT: l3_off = raw.l3_off, ip_len = 0.
+ * ip_len == 0 is the existing "no frame" value (CGCK_MIXED and cgck_rss_desc
+ * answer CGCK_BAD_LEN, queue 0xFF; cgck_steer bins it as unsteered), so the three
+ * calls compose after this one with no special case.  cls[k] = class | flags.
+ * count[] are running counters (+=, like `bad` and qcount): [c] frames of class c
+ * for the ten classes, [10] frames with CGCK_L2_BCAST or CGCK_L2_MCAST
+ * (if_imcasts), [11] frames with CGCK_L2_VLAN.  count[5..9] are what
+ * ipstat.ips_toosmall / ips_badvers / ips_badhlen / ips_badlen / ips_tooshort
+ * would have counted, with one difference: ip_input verifies the header sum
+ * before it looks at ip_len (ip_input.c:45-67), so a frame with both a bad sum and
+ * a bad length is counted there as ips_badsum and here by its length class only
+ * (this call sums nothing; CGCK_VERIFY does, afterwards).
+ *
+ * Execution.  Asynchronous on `stream` (NULL: the context's).  n == 0 returns 0,
+ * launches nothing and writes nothing.  The frames and `raw` are never written.
+ * The library keeps no scratch for this call.  One kernel, l2d_kernel; every rule
+ * consults only the frame's first 28 bytes, and every read lies inside the 16-byte
+ * granules that hold a byte of [frame, frame + L) (cgck_rss_desc's rule).
+ * desc_out must not be raw.
+ * Measured (DESIGN.md §5.11, 16M Ethernet-framed dual-stack IMIX frames in
+ * 2048-byte slots on one MI355X): 0.50 ms with all three outputs, the same as the
+ * cgck_rss_desc that follows it on the same burst.
+ * There is no host form and no strided form: a host burst's bytes are in the
+ * host's caches for the RX window anyway, where these few compares per frame cost
+ * less than a launch; and a ring's delivered lengths differ per slot, so its caller
+ * writes an array either way.
+ * -EINVAL: a NULL ctx, res or base, or (with n > 0) a NULL raw; every output
+ * NULL; a misaligned raw or desc_out; desc_out == raw. */
+enum { /* class: low nibble of cls[k] */
+	CGCK_L2_IP4 = 0, CGCK_L2_IP6 = 1, CGCK_L2_ARP = 2, CGCK_L2_OTHER = 3, CGCK_L2_RUNT = 4,
+	CGCK_L2_TOOSMALL = 5, CGCK_L2_BADVERS = 6, CGCK_L2_BADHLEN = 7, CGCK_L2_BADLEN = 8,
+	CGCK_L2_TOOSHORT = 9, CGCK_L2_NCLASS = 10,
+};
+enum { CGCK_L2_VLAN = 1u << 4, CGCK_L2_BCAST = 1u << 6, CGCK_L2_MCAST = 1u << 7 }; /* flag bits of cls[k] */
+#define CGCK_L2_NCOUNT 12 /* counters: [class] for the ten classes, [10] BCAST or MCAST frames (if_imcasts), [11] tagged frames */
+
+typedef struct cgck_l2_res {   /* device memory; each optional (NULL); at least one non-NULL */
+	cgck_desc_t *desc_out; /* [n] */
+	uint8_t *cls;          /* [n] */
+	uint32_t *count;       /* u32[CGCK_L2_NCOUNT], running counters (+=), like `bad` and qcount */
+} cgck_l2_res_t;
+
+int cgck_l2_desc(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *raw, uint64_t n,
+		 const cgck_l2_res_t *res, void *stream);
+
 /* One dst-cache entry: the fields thread_init_dst_cache fills in struct
  * ip_socket (con-gen.c:344-349; subr.h:218-228).  16 bytes. */
 typedef struct cgck_dst_entry {
@@ -753,6 +856,10 @@ int cgck_test_burst_route_kind(uint32_t i, char *kind, size_t cap);
  * pointer may be NULL.  Needs no device and no context.  -EINVAL: queue_num
  * outside 1..128 or n above 0xFFFFFFFF. */
 int cgck_test_steer_plan(uint64_t n, uint32_t queue_num, uint32_t *tile, uint32_t *tiles, size_t *work_bytes);
+/* Frames one pass of cgck_l2_desc's grid covers on ctx's device: the launcher's
+ * workgroup cap (four per compute unit) x 256.  A burst above twice that makes
+ * every wave run three steps.  -EINVAL: a NULL ctx or frames. */
+int cgck_test_l2_pass(cgck_ctx_t *ctx, uint64_t *frames);
 
 #ifdef __cplusplus
 }
