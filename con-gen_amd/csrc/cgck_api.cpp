@@ -1,9 +1,9 @@
 // cgck_api.cpp — host side of libcgck.so: the C-ABI declared in
 // include/cgck.h.  Contexts (stream + staging), device-resident and
-// host-resident batches, registered rings, the burst server, the Toeplitz
-// RSS batch and dst-cache entry points, synthetic generation and timing.
-// The drop-in symbols and the per-thread RX / TX windows are in
-// cgck_dropin.cpp.
+// host-resident batches, registered rings, the Toeplitz RSS batch and
+// dst-cache entry points, synthetic generation and timing.  The burst
+// server's host side is in cgck_burst.cpp, the drop-in symbols and the
+// per-thread RX / TX windows are in cgck_dropin.cpp.
 //
 // Every checksum this library returns is computed by the gfx950 kernels
 // (cgck_group.hip, cgck_lane.hip); there is no host arithmetic path.  Without
@@ -11,15 +11,12 @@
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
-#include <sched.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include <atomic>
-#include <mutex>
 #include <shared_mutex>
 #include <vector>
 
@@ -57,15 +54,6 @@ static void rss_users_free(cgck_ctx *c);
 struct cgck_event {
 	hipEvent_t ev;
 };
-
-// hipFree / hipHostFree synchronise the device: with a burst server resident
-// on it (a persistent kernel) such a free waits until every server idles out
-// — 200 ms of a worker's loop (a coalesced loop whose fills outgrew the
-// staging: tools/txloop, profiles/r06/stall/), or forever while other
-// workers keep theirs busy.  So while any server is resident a buffer is not
-// freed but parked, and parked buffers are freed once the last server has
-// closed (burst_close).
-static void free_or_park(void *p, bool host);
 
 int cgck::grow_host(void **p, size_t *cap, size_t need)
 {
@@ -176,7 +164,7 @@ extern "C" int cgck_ctx_destroy(cgck_ctx_t *c)
 	if (!c)
 		return 0;
 	(void)hipSetDevice(c->device);
-	if (c->bbox)
+	if (c->srv.box)
 		(void)cgck_burst_close(c);
 	(void)CGCK_SYNC(c->stream);
 	(void)hipStreamDestroy(c->stream);
@@ -306,574 +294,6 @@ extern "C" int cgck_desc(cgck_ctx_t *c, void *base, const cgck_desc_t *desc, uin
 }
 
 // --------------------------------------------------------------------------
-// Burst server (cgck_group.hip): small host-resident batches without a launch
-// or a stream synchronisation each
-// --------------------------------------------------------------------------
-
-static double now_s()
-{
-	struct timespec ts;
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return ts.tv_sec + ts.tv_nsec * 1e-9;
-}
-
-#if CGCK_LAB
-hipError_t cgck::lab_sync(const char *where, hipStream_t st)
-{
-	const double t0 = now_s();
-	const hipError_t e = hipStreamSynchronize(st);
-	if (now_s() - t0 > 0.02)
-		fprintf(stderr, "cgck lab: hipStreamSynchronize at %s took %.1f ms\n", where, (now_s() - t0) * 1e3);
-	return e;
-}
-#endif
-
-// (Re)launch the server's K workgroups; the first request each serves is
-// the one after start_seq.
-#if CGCK_LAB
-static thread_local uint64_t t_lab_host[2]; // cgck_lab_burst_times
-thread_local double t_lab_post[16];         // cgck_lab_post_times (cgck_dropin.cpp), TSC ticks
-#define LAB_TICK(i, t0) (t_lab_post[2 * (i)] += (double)(__builtin_ia32_rdtsc() - (t0)), t_lab_post[2 * (i) + 1] += 1)
-#endif
-
-// Lab A/B bits of the server kernel ($CGCK_SERVER_OPTS; 0 in the product).
-static uint32_t server_opts()
-{
-	static const uint32_t v = [] {
-		const char *e = CGCK_ENV("CGCK_SERVER_OPTS");
-		return e && *e ? (uint32_t)strtoul(e, nullptr, 0) : 0u;
-	}();
-	return v;
-}
-
-// Server launches in this process: a relay word left by one launch (in
-// device memory a later server may get again) never matches another's tag.
-static std::atomic<uint32_t> g_burst_epoch{0};
-
-// No server kernel runs while a host mapping changes.  cgck_host_register /
-// _unregister (and burst open / close) take g_map_wr, raise g_map_changing,
-// wait until no context with a server is inside a request (its bbusy word),
-// and drain every open server (the next request relaunches it).  A request
-// (post, wait, relaunch) runs inside a MapGuard on its own context: it sets
-// the context's bbusy and then checks g_map_changing (both sequentially
-// consistent, so either the writer sees the context busy or the request sees
-// the change and steps back until it is over).  The request path thus writes
-// only its own context's line and reads a line no request writes: no
-// process-wide lock or shared read-modify-write per request (32 workers each
-// posting bursts do not bounce a lock line).  g_srv lists the
-// contexts with an open server (changed under g_map_wr).
-namespace {
-std::mutex g_map_wr;
-std::mutex g_park_mu;
-std::vector<std::pair<void *, bool>> g_parked; // (buffer, host)
-std::atomic<uint32_t> g_map_changing{0};
-std::mutex g_srv_mu;
-std::vector<cgck_ctx *> g_srv;
-
-class MapGuard {
-      public:
-	explicit MapGuard(cgck_ctx *c) : c_(c)
-	{
-		for (;;) {
-			__atomic_store_n(&c_->bbusy, 1u, __ATOMIC_SEQ_CST);
-			if (!g_map_changing.load(std::memory_order_seq_cst))
-				return;
-			__atomic_store_n(&c_->bbusy, 0u, __ATOMIC_RELEASE);
-			for (uint32_t k = 0; g_map_changing.load(std::memory_order_acquire); k++) {
-				if (k < 4096)
-					__builtin_ia32_pause();
-				else
-					sched_yield();
-			}
-		}
-	}
-	~MapGuard() { __atomic_store_n(&c_->bbusy, 0u, __ATOMIC_RELEASE); }
-	MapGuard(const MapGuard &) = delete;
-	MapGuard &operator=(const MapGuard &) = delete;
-
-      private:
-	cgck_ctx *c_;
-};
-
-// The writer side: g_map_wr held; no request of any server context is in
-// flight on the host side when it returns (ended by ~MapChange).
-class MapChange {
-      public:
-	MapChange() : lk_(g_map_wr)
-	{
-		g_map_changing.store(1, std::memory_order_seq_cst);
-		// (the list copied: no lock held while waiting; it cannot change
-		// meanwhile, burst open / close take g_map_wr)
-		std::vector<cgck_ctx *> srv;
-		{
-			std::lock_guard<std::mutex> lk(g_srv_mu);
-			srv = g_srv;
-		}
-		for (cgck_ctx *c : srv)
-			for (uint32_t k = 0; __atomic_load_n(&c->bbusy, __ATOMIC_SEQ_CST); k++) {
-				if (k < 4096)
-					__builtin_ia32_pause();
-				else
-					sched_yield();
-			}
-	}
-	~MapChange() { g_map_changing.store(0, std::memory_order_release); }
-	MapChange(const MapChange &) = delete;
-	MapChange &operator=(const MapChange &) = delete;
-
-      private:
-	std::lock_guard<std::mutex> lk_;
-};
-} // namespace
-
-static void free_or_park(void *p, bool host)
-{
-	bool resident;
-	{
-		std::lock_guard<std::mutex> lk(g_srv_mu);
-		resident = !g_srv.empty();
-	}
-	if (resident) {
-		std::lock_guard<std::mutex> lk(g_park_mu);
-		g_parked.emplace_back(p, host);
-		return;
-	}
-	if (host)
-		(void)hipHostFree(p);
-	else
-		(void)hipFree(p);
-}
-
-// The parked buffers, freed once no server is resident (caller: after a
-// close took its server out of g_srv).
-static void free_parked()
-{
-	{
-		std::lock_guard<std::mutex> lk(g_srv_mu);
-		if (!g_srv.empty())
-			return;
-	}
-	std::vector<std::pair<void *, bool>> v;
-	{
-		std::lock_guard<std::mutex> lk(g_park_mu);
-		v.swap(g_parked);
-	}
-	for (const auto &x : v) {
-		if (x.second)
-			(void)hipHostFree(x.first);
-		else
-			(void)hipFree(x.first);
-	}
-}
-
-static bool burst_all_alive(const cgck_ctx *c);
-static int burst_restart(cgck_ctx *c);
-
-// The stop word the leader polls: beside the device-memory doorbell (written
-// through the large BAR, pushed out of the write-combining buffer) or in the
-// host mailbox.
-static void burst_stop(cgck_ctx *c, uint32_t v)
-{
-	if (c->bdoor) {
-		__builtin_ia32_sfence();
-		__atomic_store_n((uint32_t *)(c->bdoor + 2), v, __ATOMIC_RELAXED);
-		__builtin_ia32_sfence();
-	}
-	__atomic_store_n(&c->bbox->stop, v, __ATOMIC_RELEASE);
-}
-
-// Requests complete in order, so the last one known complete is the latest
-// seq collected, whatever order the posted requests are collected in (the
-// pipelined windows collect a TX fill, then the older RX burst that shares
-// nothing with it).  bdone only moves forward: a relaunch starts after it, and
-// one that started after an older seq would have its leader poll a slot the
-// host has since posted a later request into.
-static void burst_done_at(cgck_ctx *c, uint32_t seq)
-{
-	if ((int32_t)(seq - c->bdone) > 0)
-		c->bdone = seq;
-}
-
-// Serve every request posted to c and not collected yet (the seqs after
-// bdone up to bseq: a pipelined window's burst or fill), relaunching the
-// server if it idled out, without collecting them: their outputs stay in
-// their slots for the poster's own collect, which then finds them done.
-// The caller holds a MapChange, so neither seq moves meanwhile.
-// A request not served in 2 s is abandoned (the next launch starts after
-// it; its poster's collect times out): it must not be served after the
-// mapping it reads has changed.
-static void burst_finish_posted(cgck_ctx *c)
-{
-	BurstBox *b = c->bbox;
-	for (uint32_t s = c->bdone, k = 0; s != c->bseq && k < 4; k++) {
-		s = burst_next(s);
-		const uint32_t n = (uint32_t)(c->breq[s & 1] >> 32) & ~kBurstVram;
-		const uint32_t W = burst_wgs(n, c->bwgs, c->bper);
-		const double t0 = now_s();
-		uint32_t j = 0;
-		for (uint32_t spin = 0; j < W;) {
-			if ((int32_t)(__atomic_load_n(&b->done[j], __ATOMIC_ACQUIRE) - s) >= 0) {
-				j++;
-				continue;
-			}
-			__builtin_ia32_pause();
-			if ((++spin & 1023) != 0)
-				continue;
-			if (!burst_all_alive(c) && burst_restart(c) != 0)
-				return;
-			if (now_s() - t0 > 2.0) {
-				c->bdone = c->bseq;
-				return;
-			}
-		}
-		// served: the relaunch after the mapping change starts after it (its
-		// outputs stay in the slot for the poster's collect, which finds its
-		// done words past it), so it is never served again over the new mapping
-		burst_done_at(c, s);
-	}
-}
-
-// Stop every open server and wait until its workgroups have left (caller
-// holds a MapChange, so no request is posted meanwhile).  Requests
-// already posted are served first (burst_finish_posted): a relaunch after
-// the mapping change must not read or store through a range that is gone.
-static void burst_quiesce_all()
-{
-	std::lock_guard<std::mutex> lk(g_srv_mu);
-	for (cgck_ctx *c : g_srv) {
-		if (!c->bbox)
-			continue;
-		(void)hipSetDevice(c->device);
-		burst_finish_posted(c);
-		burst_stop(c, 1u);
-		(void)CGCK_SYNC(c->bstream);
-		burst_stop(c, 0u);
-	}
-}
-
-static int burst_launch(cgck_ctx *c, uint32_t start_seq)
-{
-	uint32_t epoch;
-	while ((epoch = g_burst_epoch.fetch_add(1, std::memory_order_relaxed) + 1) == 0)
-		;
-	for (uint32_t j = 0; j < c->bwgs; j++)
-		__atomic_store_n(&c->bbox->alive[j], (uint8_t)1, __ATOMIC_RELEASE);
-	hipError_t e = launch_burst_server(c->bbox_dev, c->bdoor ? c->bdoor : c->bbox_dev->req,
-					   c->bdoor ? (const uint32_t *)(c->bdoor + 2) : &c->bbox_dev->stop, c->bstage_dev, c->bvblk,
-					   c->bscratch, c->bresp_dev, c->brelay, c->d_zero, (uint32_t)c->bstage_cap,
-					   c->bmax, c->bwgs, c->bper, start_seq, epoch, server_opts(), c->bstream);
-	if (e != hipSuccess) {
-		for (uint32_t j = 0; j < c->bwgs; j++)
-			__atomic_store_n(&c->bbox->alive[j], (uint8_t)0, __ATOMIC_RELEASE);
-		return set_err(-EIO, "burst server launch: %s", hipGetErrorString(e));
-	}
-	return 0;
-}
-
-static bool burst_all_alive(const cgck_ctx *c)
-{
-	for (uint32_t j = 0; j < c->bwgs; j++)
-		if (!__atomic_load_n(&c->bbox->alive[j], __ATOMIC_ACQUIRE))
-			return false;
-	return true;
-}
-
-// A workgroup has idled out (or the server is draining): stop the rest,
-// wait until every workgroup has left, relaunch them for the requests after
-// the last one completed (the pending ones are still in their slots).
-static int burst_restart(cgck_ctx *c)
-{
-	(void)hipSetDevice(c->device);
-	burst_stop(c, 1u);
-	const hipError_t e = CGCK_SYNC(c->bstream);
-	burst_stop(c, 0u);
-	if (e != hipSuccess)
-		return set_err(-EIO, "burst server drain: %s", hipGetErrorString(e));
-	return burst_launch(c, c->bdone);
-}
-
-// A request costs the poll, the round trips of the request block and the
-// packet bytes, and the outputs' write acknowledgements (~5 us for a small
-// one, tools/pingpong) instead of a launch and a stream synchronisation
-// (~9.4 us for an empty kernel).  Up to kBurstOneWG packets one workgroup
-// serves it from one wide read of the block; larger requests are split over
-// up to K workgroups, each reading its slice of the descriptors and the
-// packet bytes where they lie.  Registered packets are copied into the block
-// up to 32 KiB of block (one read for a small request) and read in place
-// above; in-place requests carry their range, which the server checks every
-// descriptor against.  The TX window's flush goes through cgck_desc_host of
-// its ring range, so it takes the server whenever it fits.  Which requests go
-// to the server is the caller's choice at open: cgck_burst_open's max_pkts
-// and max_bytes (packet bytes per request).  The launch path's many
-// workgroups read the fabric faster for hundreds of frames of >= 576 B (256 x
-// 576 B: 22.8 vs 29.2 us), the server wins below ~100 KiB of packet bytes
-// (profiles/r03/burst), so max_bytes ~96 KiB routes a mixed workload best.
-// $CGCK_SERVER_PKTS / _COPY override the caps for A/B runs (lab build).
-//
-// Two requests may be outstanding (two slots, cgck_internal.h): a posted
-// request is collected (burst_wait, then its outputs read from its slot)
-// before its slot is posted to again.  The synchronous callers post and
-// collect at once; the pipelined windows (cgck_rx_post, cgck_tx_post) leave
-// one request posted while the stack works, and a later post that needs its
-// slot collects it first (burst_slot_free).
-static size_t env_size(const char *v, size_t dflt)
-{
-	return v && *v ? (size_t)strtoull(v, nullptr, 0) : dflt;
-}
-static const uint64_t kServerPkts = env_size(CGCK_ENV("CGCK_SERVER_PKTS"), kServerPktsDefault);
-static const size_t kServerCopy = env_size(CGCK_ENV("CGCK_SERVER_COPY"), kServerCopyDefault);
-
-// (BurstLayout, burst_layout and the predicates below: cgck_route.h, which
-// burst_route names a request's route from)
-
-// Does a request of n packets of at most max_len bytes, `data` packet bytes
-// of which `staged` are copied into the block (0 when read in place), go to
-// the server?
-static bool burst_fits(const cgck_ctx *c, uint64_t n, uint32_t max_len, size_t staged, size_t data)
-{
-	(void)max_len;
-	return c->bbox && burst_fits_caps(c->bmax, kServerPkts, c->bstage_cap, c->bmax_bytes, n, staged, data);
-}
-
-static uint8_t *burst_block(const cgck_ctx *c, uint32_t seq) { return c->bstage + (size_t)(seq & 1) * c->bstage_cap; }
-
-static const uint8_t *burst_resp(const cgck_ctx *c, uint32_t seq)
-{
-	return c->bresp + (size_t)(seq & 1) * burst_resp_slot(c->bmax);
-}
-
-// Wait until request seq (n packets) is served.  Requests complete in order,
-// so a workgroup's done word at or past seq means its slice is in.
-static int burst_wait(cgck_ctx *c, uint32_t seq, uint32_t n, uint64_t range)
-{
-#if CGCK_LAB
-	const uint64_t tl0 = __builtin_ia32_rdtsc();
-#endif
-	MapGuard map_g(c);
-#if CGCK_LAB
-	LAB_TICK(4, tl0);
-	const uint64_t tl1 = __builtin_ia32_rdtsc();
-#endif
-	BurstBox *b = c->bbox;
-	const uint32_t W = burst_wgs(n, c->bwgs, c->bper);
-	const double t0 = now_s();
-	uint32_t spin = 0;
-	for (uint32_t j = 0; j < W;) {
-		if ((int32_t)(__atomic_load_n(&b->done[j], __ATOMIC_ACQUIRE) - seq) >= 0) {
-			j++;
-			continue;
-		}
-		__builtin_ia32_pause();
-		if ((++spin & 1023) != 0)
-			continue;
-#if CGCK_LAB
-		// lab: a wait past 20 ms says what the server looked like (the
-		// driver's bench once saw one loop iteration take the server's
-		// 200 ms idle bound)
-		if (now_s() - t0 > 0.02 && !(spin & ((1u << 20) - 1))) {
-			char dw[200];
-			int at = 0;
-			for (uint32_t k = 0; k < c->bwgs && at < (int)sizeof(dw) - 16; k++)
-				at += snprintf(dw + at, sizeof(dw) - at, " %u:%u%s", k, __atomic_load_n(&b->done[k], __ATOMIC_ACQUIRE),
-					       __atomic_load_n(&b->alive[k], __ATOMIC_ACQUIRE) ? "" : "x");
-			fprintf(stderr,
-				"cgck lab: wait %.1f ms for seq %u (n %u, W %u): bseq %u bdone %u breq %#llx %#llx "
-				"slots %p %p done/alive%s\n",
-				(now_s() - t0) * 1e3, seq, n, W, c->bseq, c->bdone, (unsigned long long)c->breq[0],
-				(unsigned long long)c->breq[1], (void *)c->bslot[0], (void *)c->bslot[1], dw);
-		}
-#endif
-		if (!burst_all_alive(c)) {
-			// a workgroup exited between the post and its last poll: drain
-			// and relaunch for the pending requests (slices already served
-			// are not served again: the server's recheck)
-			int rc = burst_restart(c);
-			if (rc)
-				return rc;
-		}
-		if (now_s() - t0 > 2.0) {
-			// Drain before returning, so no workgroup touches the caller's
-			// memory after the call (each leaves within its idle bound),
-			// and say which slices never came back.
-			char miss[160];
-			int at = 0;
-			for (uint32_t k = 0; k < W && at < (int)sizeof(miss) - 12; k++)
-				if ((int32_t)(__atomic_load_n(&b->done[k], __ATOMIC_ACQUIRE) - seq) < 0)
-					at += snprintf(miss + at, sizeof(miss) - at, " %u:%u", k,
-						       __atomic_load_n(&b->done[k], __ATOMIC_ACQUIRE));
-			miss[at] = 0;
-			burst_stop(c, 1u);
-			(void)CGCK_SYNC(c->bstream);
-			burst_stop(c, 0u);
-			uint64_t relay[3] = {0, 0, 0};
-			(void)hipMemcpy(relay, c->brelay, sizeof(relay), hipMemcpyDeviceToHost);
-			burst_done_at(c, seq); // abandoned: the next launch starts after it
-			return set_err(-ETIMEDOUT,
-				       "burst server: request %u (n %u, W %u) not served in 2 s; missing (wg:done)%s; "
-				       "relay %#llx %#llx %#llx",
-				       seq, n, W, miss, (unsigned long long)relay[0], (unsigned long long)relay[1],
-				       (unsigned long long)relay[2]);
-		}
-	}
-#if CGCK_LAB
-	t_lab_host[1] = (uint64_t)(now_s() * 1e9);
-	LAB_TICK(5, tl1);
-#endif
-	burst_done_at(c, seq);
-	if (__atomic_load_n(&b->refused[seq & 1], __ATOMIC_ACQUIRE) == seq)
-		return set_err(-EIO,
-			       "burst server: request %u refused (block header, or a descriptor outside the block or "
-			       "past the %llu-byte range)",
-			       seq, (unsigned long long)range);
-	return 0;
-}
-
-// Collect a posted request: wait for it and copy its outputs where its
-// poster asked; frees its slot.
-int cgck::burst_collect(cgck_ctx *c, BurstPending *p)
-{
-	if (!p->seq)
-		return p->rc;
-	const uint32_t seq = p->seq;
-	p->seq = 0;
-	if (c->bslot[seq & 1] == p)
-		c->bslot[seq & 1] = nullptr;
-	// The GPU wrote the done words and the response, so none of their lines
-	// is in this core's caches: a posted request is usually served by now,
-	// so start those misses together instead of one after the other.
-	{
-		const uint8_t *o = burst_resp(c, seq);
-		__builtin_prefetch(&c->bbox->done[0]);
-		const uint32_t lim = 4 * p->n < 512 ? 4 * p->n : 512;
-		for (uint32_t at = 0; at < lim; at += 64) {
-			if (p->out)
-				__builtin_prefetch(o + at);
-			if (p->meta)
-				__builtin_prefetch(o + burst_meta_off(p->n) + at);
-		}
-	}
-	int rc = burst_wait(c, seq, p->n, p->range);
-	if (rc == 0) {
-#if CGCK_LAB
-		const uint64_t tc0 = __builtin_ia32_rdtsc();
-#endif
-		const uint8_t *o = burst_resp(c, seq);
-		if (p->out)
-			memcpy(p->out, o, 4 * (size_t)p->n);
-		if (p->meta)
-			memcpy(p->meta, o + burst_meta_off(p->n), 4 * (size_t)p->n);
-		if (p->verdict)
-			memcpy(p->verdict, o + burst_ver_off(p->n), p->n);
-#if CGCK_LAB
-		LAB_TICK(2, tc0);
-#endif
-	}
-	p->rc = rc;
-	return rc;
-}
-
-int cgck::burst_ready(cgck_ctx *c, const BurstPending *p)
-{
-	if (!p->seq)
-		return 1;
-	const uint32_t W = burst_wgs(p->n, c->bwgs, c->bper);
-	for (uint32_t j = 0; j < W; j++)
-		if ((int32_t)(__atomic_load_n(&c->bbox->done[j], __ATOMIC_ACQUIRE) - p->seq) < 0) {
-			// not served yet: a server that idled out between the post and
-			// its last poll is relaunched here, as burst_wait would, so a
-			// caller that only ever asks does not wait forever
-			if (!burst_all_alive(c)) {
-				MapGuard map_g(c);
-				(void)burst_restart(c);
-			}
-			return 0;
-		}
-	return 1;
-}
-
-// The block of the next request (L.bytes of it), with its slot free: a
-// posted request still holding that slot is collected first.  A block of up
-// to kBurstVramMax bytes (a drop-in call on up to ~1.9 KiB, a burst of up to
-// ~165 descriptors in place) goes to the slot's device-memory block when the
-// device has one: the host writes it through the large BAR (write-combined)
-// and the server reads it locally instead of across the fabric
-// (tools/vramdb: 4.70 against 5.55 us for the bare round trip of a 4 KiB
-// block, profiles/r06/).  Larger blocks stay in host staging: the host's
-// write-combined stores cost ~0.13 us a KiB (0.53 us for 4 KiB against 0.06
-// into host memory), which is the worker's time.  So do the blocks of posted
-// requests (the pipelined / coalesced windows): their latency is hidden
-// behind the stack's work, while the write-combined stores would be the
-// worker's own; only their doorbell goes to device memory.
-static const size_t kBurstVramMax = env_size(CGCK_ENV("CGCK_BURST_VRAM_MAX"), 2048); // lab A/B: the bound
-static const size_t kBurstVramPostedMax = env_size(CGCK_ENV("CGCK_BURST_VRAM_POSTED_MAX"), 0); // lab A/B: posted ones
-static int burst_slot_free(cgck_ctx *c, const BurstLayout &L, uint8_t **block, bool posted = false)
-{
-	const uint32_t seq = burst_next(c->bseq);
-	if (BurstPending *p = c->bslot[seq & 1]) {
-		const int rc = burst_collect(c, p); // its poster reads p->rc
-		(void)rc;
-	}
-	c->bnext_vram = c->bvblk && L.bytes <= (posted ? kBurstVramPostedMax : kBurstVramMax) && L.bytes <= kBurstFirst;
-	*block = c->bnext_vram ? c->bvblk + (size_t)(seq & 1) * kBurstFirst : burst_block(c, seq);
-	return 0;
-}
-
-// Post the request whose descriptors (and, for base_dev == nullptr, packet
-// bytes) are in the next block; returns its seq.
-static int burst_post(cgck_ctx *c, const uint8_t *base_dev, uint64_t range, uint64_t n, uint32_t flags,
-		      uint32_t max_len, const BurstLayout &L, uint32_t *seq_out, const DescSplit *split = nullptr)
-{
-	MapGuard map_g(c);
-	BurstBox *b = c->bbox;
-	const uint32_t seq = burst_next(c->bseq);
-	const bool vram = c->bnext_vram;
-	BurstReq *r = (BurstReq *)(vram ? c->bvblk + (size_t)(seq & 1) * kBurstFirst : burst_block(c, seq));
-	r->n = (uint32_t)n;
-	r->flags = flags;
-	r->max_len = max_len;
-	r->bytes = (uint32_t)L.bytes;
-	r->base = (uint64_t)(uintptr_t)base_dev;
-	r->range = base_dev ? range : 0;
-	r->d_off = (uint32_t)L.d_off;
-	r->p_off = (uint32_t)L.p_off;
-	r->n1 = split ? split->n1 : 0;
-	r->flags2 = split ? split->flags2 : 0;
-	c->bseq = seq;
-#if CGCK_LAB
-	t_lab_host[0] = (uint64_t)(now_s() * 1e9);
-#endif
-	const uint64_t word = (uint64_t)seq | (uint64_t)((uint32_t)n | (vram ? kBurstVram : 0u)) << 32;
-	c->breq[seq & 1] = word;
-	if (c->bdoor) {
-		// The block's stores (write-combined device memory, or host memory)
-		// are out before the doorbell, and the doorbell leaves the
-		// write-combining buffer now rather than at its next eviction.
-		__builtin_ia32_sfence();
-		__atomic_store_n(&c->bdoor[seq & 1], word, __ATOMIC_RELAXED);
-		__builtin_ia32_sfence();
-	} else {
-		__atomic_store_n(&b->req[seq & 1], word, __ATOMIC_RELEASE);
-	}
-	*seq_out = seq;
-	if (!burst_all_alive(c)) {
-		int rc = burst_restart(c); // idled out: a new server picks the pending requests up
-		if (rc)
-			return rc;
-	}
-	return 0;
-}
-
-// Post and collect at once: outputs at burst_resp(c, *seq_out).
-static int burst_serve(cgck_ctx *c, const uint8_t *base_dev, uint64_t range, uint64_t n, uint32_t flags,
-		       uint32_t max_len, const BurstLayout &L, uint32_t *seq_out)
-{
-	int rc = burst_post(c, base_dev, range, n, flags, max_len, L, seq_out);
-	if (rc)
-		return rc;
-	return burst_wait(c, *seq_out, (uint32_t)n, range);
-}
-
-// --------------------------------------------------------------------------
 // Host-resident batch
 // --------------------------------------------------------------------------
 //
@@ -908,6 +328,39 @@ static void *registered_ptr(void *p, size_t bytes)
 	return a.devicePointer;
 }
 
+// Does every descriptor lie inside the `bytes` given?  -EINVAL in `who`'s name
+// otherwise.  sum (optional): the longest ip_len and the packets' bytes, each
+// padded to 16.
+static int desc_range_check(const char *who, const cgck_desc_t *desc, uint64_t n, size_t bytes, DescSummary *sum = nullptr)
+{
+	DescSummary s = {0, 0};
+	for (uint64_t i = 0; i < n; i++) {
+		s.max_len = desc[i].ip_len > s.max_len ? desc[i].ip_len : s.max_len;
+		const uint64_t end = desc[i].frame_off + desc[i].l3_off + desc[i].ip_len;
+		if (end > bytes || end < desc[i].frame_off)
+			return set_err(-EINVAL, "%s: descriptor %llu reaches past the %zu bytes given", who,
+				       (unsigned long long)i, bytes);
+		s.pkt_bytes += ((size_t)desc[i].ip_len + 15) & ~(size_t)15;
+	}
+	if (sum)
+		*sum = s;
+	return 0;
+}
+
+// Copy each packet of [base, ...) to a 16-byte-padded offset of `dst` and
+// describe it there: d[i] is desc[i]'s packet relative to dst.
+static void gather_packets(uint8_t *dst, cgck_desc_t *d, const void *base, const cgck_desc_t *desc, uint64_t n)
+{
+	size_t at = 0;
+	for (uint64_t i = 0; i < n; i++) {
+		memcpy(dst + at, (const uint8_t *)base + desc[i].frame_off + desc[i].l3_off, desc[i].ip_len);
+		d[i].frame_off = at;
+		d[i].l3_off = 0;
+		d[i].ip_len = desc[i].ip_len;
+		at += ((size_t)desc[i].ip_len + 15) & ~(size_t)15;
+	}
+}
+
 // desc_host, or (pend != nullptr) its posted form: when the request goes to
 // the burst server it is left posted and *pend records where its outputs go
 // (1 is returned; burst_collect finishes it), otherwise it is computed at
@@ -925,16 +378,12 @@ static int desc_host_impl(cgck_ctx *c, void *base, size_t bytes, const cgck_desc
 		split = nullptr;
 	if (!base || !desc)
 		return set_err(-EINVAL, "cgck_desc_host: NULL base or descriptors");
-	size_t pkt_bytes = sum ? sum->pkt_bytes : 0;
-	uint32_t max_len = sum ? sum->max_len : 0;
-	for (uint64_t i = 0; i < n && !sum; i++) {
-		max_len = desc[i].ip_len > max_len ? desc[i].ip_len : max_len;
-		const uint64_t end = desc[i].frame_off + desc[i].l3_off + desc[i].ip_len;
-		if (end > bytes || end < desc[i].frame_off)
-			return set_err(-EINVAL, "cgck_desc_host: descriptor %llu reaches past the %zu bytes given",
-				       (unsigned long long)i, bytes);
-		pkt_bytes += ((size_t)desc[i].ip_len + 15) & ~(size_t)15;
-	}
+	int rc;
+	DescSummary own;
+	if (!sum && (rc = desc_range_check("cgck_desc_host", desc, n, bytes, &own)))
+		return rc;
+	const size_t pkt_bytes = (sum ? sum : &own)->pkt_bytes;
+	const uint32_t max_len = (sum ? sum : &own)->max_len;
 	// Kernel shape from the context's length hint (default 1500: the group
 	// kernel's 16 packets per block), not from the batch: a host-resident
 	// burst is bound by PCIe round trips, which many small blocks overlap —
@@ -947,7 +396,6 @@ static int desc_host_impl(cgck_ctx *c, void *base, size_t bytes, const cgck_desc
 	RegRange rr;
 	void *dev_base = reg_find(base, bytes, &rr) ? (void *)(rr.dev + ((uint8_t *)base - rr.lo))
 						    : registered_ptr(base, bytes);
-	int rc;
 	// Server requests copy the packet bytes into the request block (one wide
 	// read) unless they are registered and either larger than that read or
 	// stored to in place; a pageable batch with in-place stores takes the
@@ -959,41 +407,25 @@ static int desc_host_impl(cgck_ctx *c, void *base, size_t bytes, const cgck_desc
 	const bool in_place = burst_in_place(dev_base != nullptr, store, pend != nullptr, pkt_bytes, n, kServerCopy);
 	// (an IPv6 or mixed batch takes the launch path: the server's bodies are IPv4)
 	if (burst_flags_ok(flags, in_place) &&
-	    burst_fits(c, n, max_len, in_place ? 0 : pkt_bytes, pkt_bytes)) {
+	    burst_fits(c, n, in_place ? 0 : pkt_bytes, pkt_bytes)) {
 		// the resident server: no launch, no stream sync
 		const BurstLayout L = burst_layout(in_place ? 0 : pkt_bytes, n);
-		uint8_t *h;
-		if ((rc = burst_slot_free(c, L, &h, pend != nullptr)))
-			return rc;
+		const BurstBlock blk = burst_next_block(c, L, pend != nullptr);
+		uint8_t *h = blk.p;
 		cgck_desc_t *d = (cgck_desc_t *)(h + L.d_off);
-		if (in_place) {
+		if (in_place)
 			memcpy(d, desc, 12 * n);
-		} else {
-			size_t at = 0;
-			for (uint64_t i = 0; i < n; i++) {
-				memcpy(h + L.p_off + at, (const uint8_t *)base + desc[i].frame_off + desc[i].l3_off,
-				       desc[i].ip_len);
-				d[i].frame_off = at;
-				d[i].l3_off = 0;
-				d[i].ip_len = desc[i].ip_len;
-				at += ((size_t)desc[i].ip_len + 15) & ~(size_t)15;
-			}
-		}
+		else
+			gather_packets(h + L.p_off, d, base, desc, n);
 		uint32_t seq;
-		if ((rc = burst_post(c, in_place ? (const uint8_t *)dev_base : nullptr, bytes, n, flags, max_len, L, &seq,
-				     split)))
+		if ((rc = burst_post(c, blk, in_place ? (const uint8_t *)dev_base : nullptr, bytes, n, flags, max_len, L,
+				     &seq, split)))
 			return rc;
 		BurstPending now;
 		BurstPending *q = pend ? pend : &now;
-		q->seq = seq;
-		q->n = (uint32_t)n;
-		q->range = bytes;
-		q->out = out;
-		q->meta = meta;
-		q->verdict = verdict;
-		q->rc = 0;
+		*q = BurstPending{seq, (uint32_t)n, bytes, out, meta, verdict, 0};
 		if (pend) {
-			c->bslot[seq & 1] = pend;
+			burst_hold(c, pend);
 			return 1;
 		}
 		return burst_collect(c, &now);
@@ -1019,18 +451,10 @@ static int desc_host_impl(cgck_ctx *c, void *base, size_t bytes, const cgck_desc
 			return rc;
 		uint8_t *h = c->h_stage;
 		cgck_desc_t *d = (cgck_desc_t *)(h + d_off);
-		if (dev_base) {
+		if (dev_base)
 			memcpy(d, desc, 12 * n);
-		} else {
-			size_t at = 0;
-			for (uint64_t i = 0; i < n; i++) {
-				memcpy(h + at, (const uint8_t *)base + desc[i].frame_off + desc[i].l3_off, desc[i].ip_len);
-				d[i].frame_off = at;
-				d[i].l3_off = 0;
-				d[i].ip_len = desc[i].ip_len;
-				at += ((size_t)desc[i].ip_len + 15) & ~(size_t)15;
-			}
-		}
+		else
+			gather_packets(h, d, base, desc, n);
 		uint32_t *o = (uint32_t *)(h + o_off);
 		uint32_t *m = meta ? (uint32_t *)(h + m_off) : nullptr;
 		uint8_t *v = h + v_off;
@@ -1139,16 +563,14 @@ extern "C" int cgck_burst_request(cgck_ctx_t *c, const void *dev_base, uint64_t 
 	uint32_t max_len = 0;
 	for (uint64_t i = 0; i < n; i++)
 		max_len = desc[i].ip_len > max_len ? desc[i].ip_len : max_len;
-	if (!burst_fits(c, n, max_len, 0, 0))
+	if (!burst_fits(c, n, 0, 0))
 		return set_err(-ENOSPC, "cgck_burst_request: no burst server open on the context, or %llu packets "
 					"exceed its capacity", (unsigned long long)n);
 	const BurstLayout L = burst_layout(0, n);
-	uint8_t *h;
-	if ((rc = burst_slot_free(c, L, &h)))
-		return rc;
-	memcpy(h + L.d_off, desc, 12 * n);
+	const BurstBlock blk = burst_next_block(c, L);
+	memcpy(blk.p + L.d_off, desc, 12 * n);
 	uint32_t seq;
-	if ((rc = burst_serve(c, (const uint8_t *)dev_base, range, n, flags, max_len, L, &seq)))
+	if ((rc = burst_serve(c, blk, (const uint8_t *)dev_base, range, n, flags, max_len, L, &seq)))
 		return rc;
 	const uint8_t *o = burst_resp(c, seq);
 	if (out)
@@ -1228,8 +650,7 @@ extern "C" int cgck_host_register(void *ptr, size_t bytes)
 			       "and re-faults under a registration; register a mapping of its own (mmap, hugetlbfs, the "
 			       "transport's pool)",
 			       ptr, bytes);
-	MapChange map_c;
-	burst_quiesce_all();
+	MapChange map_c; // no request in flight, every server drained
 	HIP_TRY(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
 	void *dev = nullptr;
 	if (hipHostGetDevicePointer(&dev, ptr, 0) != hipSuccess || !dev) {
@@ -1256,8 +677,7 @@ extern "C" int cgck_host_device_ptr(const void *ptr, size_t bytes, void **dev)
 
 extern "C" int cgck_host_unregister(void *ptr)
 {
-	MapChange map_c;
-	burst_quiesce_all();
+	MapChange map_c; // no request in flight, every server drained
 	{
 		std::unique_lock<std::shared_mutex> lk(g_reg_mu);
 		for (size_t i = 0; i < g_reg.size(); i++)
@@ -1280,12 +700,11 @@ extern "C" int cgck_host_unregister(void *ptr)
 int cgck::one_region(cgck_ctx *c, const void *src, uint32_t span, uint32_t ip_len, uint32_t flags, uint32_t *out)
 {
 	int rc;
-	if (ip_len <= 0xffff && !(flags & CGCK_STORE) && burst_fits(c, 1, ip_len, span, span)) {
+	if (ip_len <= 0xffff && !(flags & CGCK_STORE) && burst_fits(c, 1, span, span)) {
 		// the resident server: one descriptor, no launch, no stream sync
 		const BurstLayout L = burst_layout(span, 1);
-		uint8_t *h;
-		if ((rc = burst_slot_free(c, L, &h)))
-			return rc;
+		const BurstBlock blk = burst_next_block(c, L);
+		uint8_t *h = blk.p;
 		if (span)
 			memcpy(h + L.p_off, src, span);
 		cgck_desc_t *d = (cgck_desc_t *)(h + L.d_off);
@@ -1293,7 +712,7 @@ int cgck::one_region(cgck_ctx *c, const void *src, uint32_t span, uint32_t ip_le
 		d->l3_off = 0;
 		d->ip_len = (uint16_t)ip_len;
 		uint32_t seq;
-		if ((rc = burst_serve(c, nullptr, 0, 1, flags, ip_len, L, &seq)))
+		if ((rc = burst_serve(c, blk, nullptr, 0, 1, flags, ip_len, L, &seq)))
 			return rc;
 		*out = *(const uint32_t *)burst_resp(c, seq);
 		return 0;
@@ -1310,315 +729,6 @@ int cgck::one_region(cgck_ctx *c, const void *src, uint32_t span, uint32_t ip_le
 	*out = c->h_out[0];
 	return 0;
 }
-
-// The server's stream.  A resident kernel holds its hardware queue until it
-// exits, and HIP multiplexes streams over a few hardware queues
-// (GPU_MAX_HW_QUEUES, 4 by default): a plain stream may share the server's
-// queue with another stream of the process, whose work then waits behind the
-// server until it idles out.  A stream with a CU mask gets a queue of its
-// own, so the server is given one (every CU enabled: the mask only buys the
-// dedicated queue).  $CGCK_BURST_PLAIN_STREAM (lab build) takes a plain one.
-static hipError_t burst_stream(const cgck_ctx *c, hipStream_t *st)
-{
-	if (CGCK_ENV("CGCK_BURST_PLAIN_STREAM"))
-		return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-	uint32_t mask[16];
-	const int words = (c->num_cus + 31) / 32 < 16 ? (c->num_cus + 31) / 32 : 16;
-	for (int i = 0; i < words; i++)
-		mask[i] = ~0u;
-	if (c->num_cus % 32 && words == (c->num_cus + 31) / 32)
-		mask[words - 1] = (1u << (c->num_cus % 32)) - 1;
-	return hipExtStreamCreateWithCUMask(st, (uint32_t)words, mask);
-}
-
-// Resident servers a device takes from this process: each holds a hardware
-// queue of its own (burst_stream), and with 20 or more a device could not map
-// every server's queue on every XCD at once — a server's workgroups on one XCD
-// never started (a request not served in 2 s) or waited ms for the
-// scheduler's time slice (tools/txloop workers mode, 16 / 20 / 24 / 28 / 32
-// workers on one MI355X, profiles/r06/).  With 16 servers the process's
-// other streams (HIP's shared queues, GPU_MAX_HW_QUEUES = 4) starved in
-// turn: 16 more workers launching their requests recorded no burst in 0.3 s
-// (profiles/r06/doorab/workers.log), so the cap leaves them room.  con-gen's
-// 32 workers bound over a node's eight GPUs hold four each.
-constexpr uint32_t kMaxServersPerDevice = 12;
-
-// The server's stream and memory, freed (no server kernel running).
-static void burst_release(cgck_ctx *c)
-{
-	(void)hipStreamDestroy(c->bstream);
-	for (void *h : {(void *)c->bbox, (void *)c->bstage, (void *)c->bresp})
-		free_or_park(h, true);
-	for (void *d : {(void *)c->bscratch, (void *)c->brelay, (void *)c->bdoor})
-		if (d)
-			free_or_park(d, false);
-	c->bdoor = nullptr;
-	c->bvblk = nullptr;
-	c->bbox = nullptr;
-	c->bstage = nullptr;
-	c->bstage_cap = 0;
-	c->bresp = nullptr;
-	c->bscratch = nullptr;
-	c->brelay = nullptr;
-}
-
-extern "C" int cgck_burst_open(cgck_ctx_t *c, uint32_t max_pkts, size_t max_bytes, uint32_t idle_ms)
-{
-	if (!c && !(c = thread_ctx()))
-		return -ENODEV; // thread_ctx set the message
-	if (c->bbox)
-		return set_err(-EBUSY, "cgck_burst_open: already open on this context");
-	if (max_pkts == 0 || max_bytes == 0)
-		return set_err(-EINVAL, "cgck_burst_open: zero capacity");
-	if (max_pkts >= kBurstVram)
-		return set_err(-EINVAL, "cgck_burst_open: max_pkts %u", max_pkts);
-	HIP_TRY(hipSetDevice(c->device));
-	// the block holds the header, the descriptors and the packet bytes; the
-	// server's first read fetches kBurstFirst bytes whatever the request
-	const size_t cap = burst_stage_cap(max_pkts, max_bytes);
-	// two slots of outputs, each for the largest request
-	size_t resp_bytes = 2 * (size_t)burst_resp_slot(max_pkts);
-	unsigned resp_flags = hipHostMallocCoherent;
-	if (const char *e = CGCK_ENV("CGCK_BRESP_MIN")) // lab A/B: allocation size of the outputs
-		resp_bytes = resp_bytes < env_size(e, 0) ? env_size(e, 0) : resp_bytes;
-	if (const char *e = CGCK_ENV("CGCK_BRESP_FLAGS")) // lab A/B: their hipHostMalloc flags
-		resp_flags = (unsigned)env_size(e, hipHostMallocCoherent);
-	void *box = nullptr, *st = nullptr, *rs = nullptr, *bd = nullptr, *sd = nullptr, *rd = nullptr, *sc = nullptr;
-	hipError_t e = hipHostMalloc(&box, sizeof(BurstBox), hipHostMallocCoherent);
-	if (e == hipSuccess)
-		e = hipHostMalloc(&st, 2 * cap, hipHostMallocCoherent); // two request slots
-	if (e == hipSuccess)
-		e = hipHostMalloc(&rs, resp_bytes, resp_flags);
-	if (e == hipSuccess)
-		e = hipMalloc(&sc, cap);
-	// the leader's relay (one per slot, then the exit word), uncached: every poll and store
-	// goes to memory, whichever XCD's L2 the workgroups sit behind
-	void *rl = nullptr;
-	if (e == hipSuccess)
-		e = hipExtMallocWithFlags(&rl, 64, hipDeviceMallocUncached);
-	if (e == hipSuccess)
-		e = hipHostGetDevicePointer(&bd, box, 0);
-	if (e == hipSuccess)
-		e = hipHostGetDevicePointer(&sd, st, 0);
-	if (e == hipSuccess)
-		e = hipHostGetDevicePointer(&rd, rs, 0);
-	// The doorbell and the small-block slots in device memory the host writes
-	// through the large BAR (every VRAM allocation is host-mapped there:
-	// tools/vramdb), uncached so the server's polls and reads go to memory,
-	// where the host's writes land.  $CGCK_BURST_HOST_DOOR (lab build): the
-	// host-memory mailbox and blocks alone, the A/B.
-	void *vd = nullptr;
-	int large_bar = 0;
-	if (e == hipSuccess && !CGCK_ENV("CGCK_BURST_HOST_DOOR") &&
-	    hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, c->device) == hipSuccess && large_bar) {
-		if (hipExtMallocWithFlags(&vd, 64 + 2 * (size_t)kBurstFirst, hipDeviceMallocUncached) != hipSuccess) {
-			(void)hipGetLastError();
-			vd = nullptr; // the host-memory mailbox then
-		} else {
-			// zeroed by the host itself: a hipMemset is asynchronous to the
-			// host, and one still in flight when the first request's doorbell
-			// was written wiped it (request 1 never served:
-			// profiles/r06/bench_r6g)
-			memset(vd, 0, 64 + 2 * (size_t)kBurstFirst);
-			__builtin_ia32_sfence();
-		}
-	}
-	if (e == hipSuccess)
-		e = burst_stream(c, &c->bstream);
-	if (e != hipSuccess) {
-		for (void *h : {box, st, rs})
-			if (h)
-				(void)hipHostFree(h);
-		for (void *d : {sc, rl, vd})
-			if (d)
-				(void)hipFree(d);
-		return set_err(-EIO, "cgck_burst_open: %s", hipGetErrorString(e));
-	}
-	c->bdoor = (uint64_t *)vd;
-	c->bvblk = vd ? (uint8_t *)vd + 64 : nullptr;
-	c->bnext_vram = false;
-	c->breq[0] = c->breq[1] = 0;
-	memset(box, 0, sizeof(BurstBox));
-	memset(st, 0, 2 * cap);
-	c->bbox = (BurstBox *)box;
-	// one workgroup per kBurstPerWG packets of the largest request, at most
-	// kBurstMaxWG (and the device's CUs)
-	c->bper = kBurstPerWG;
-	if (const char *e = CGCK_ENV("CGCK_SERVER_PER_WG")) // lab A/B: packets per workgroup
-		c->bper = atoi(e) > 0 ? (uint32_t)atoi(e) : c->bper;
-	c->bwgs = burst_wgs(max_pkts, kBurstMaxWG, c->bper);
-	if (c->bwgs > (uint32_t)c->num_cus)
-		c->bwgs = (uint32_t)c->num_cus;
-	if (const char *e = CGCK_ENV("CGCK_SERVER_WGS")) // lab A/B: K
-		c->bwgs = atoi(e) > 0 && atoi(e) <= (int)kBurstMaxWG ? (uint32_t)atoi(e) : c->bwgs;
-	c->bbox->idle_ticks = (uint64_t)(idle_ms ? idle_ms : 200) * 100000; // 100 MHz counter
-	c->bstage = (uint8_t *)st;
-	c->bstage_cap = cap;
-	c->bstage_dev = (uint8_t *)sd;
-	c->bbox_dev = (BurstBox *)bd;
-	c->bresp = (uint8_t *)rs;
-	c->bresp_dev = (uint8_t *)rd;
-	c->bscratch = (uint8_t *)sc;
-	c->brelay = (uint64_t *)rl;
-	c->bmax = max_pkts;
-	c->bmax_bytes = max_bytes;
-	c->bseq = 0;
-	c->bdone = 0;
-	c->bbad = 0;
-	c->bslot[0] = c->bslot[1] = nullptr;
-	c->bbusy = 0;
-	std::lock_guard<std::mutex> map_wr(g_map_wr); // no mapping changes while it joins g_srv and launches
-	bool full = false;
-	uint32_t on_dev = 0;
-	{
-		std::lock_guard<std::mutex> lk(g_srv_mu);
-		for (const cgck_ctx *x : g_srv)
-			on_dev += x->device == c->device;
-		full = on_dev >= kMaxServersPerDevice;
-		if (!full)
-			g_srv.push_back(c);
-	}
-	if (full) {
-		burst_release(c);
-		return set_err(-EBUSY,
-			       "cgck_burst_open: %u burst servers already resident on device %d (each holds a hardware "
-			       "queue of its own, and a device maps only ~20 at once: beyond that, servers' workgroups "
-			       "and other streams' launches stall for ms to s, tools/txloop workers mode); bind the "
-			       "workers over more devices (cgck_thread_bind) or leave this one without",
-			       on_dev, c->device);
-	}
-	return burst_launch(c, 0);
-}
-
-// Test hooks in the product library (include/cgck.h, tests/test_gpu_burst_seq.py:
-// the driver's -m gpu gate runs the 32-bit seq-wrap test against libcgck.so).
-// cgck_test_burst_seq: restart ctx's server as if `seq` were the last request
-// served (a few seqs before the wrap).  cgck_test_burst_stale: with the
-// server running and nothing posted, set the done words of workgroups >= from
-// half the seq space ahead, as a word untouched for 2^31 requests would
-// compare; the next request must refresh them (a workgroup outside a
-// request's slices stores the seq it steps over), or a wider request after it
-// would be reported served before those workgroups wrote anything.
-extern "C" int cgck_test_burst_seq(cgck_ctx_t *c, uint32_t seq)
-{
-	if (!c || !c->bbox || c->bslot[0] || c->bslot[1])
-		return set_err(-EINVAL, "cgck_test_burst_seq: no open server, or a request posted");
-	if (seq == 0)
-		return set_err(-EINVAL, "cgck_test_burst_seq: seq 0 is never posted");
-	MapGuard map_g(c);
-	burst_stop(c, 1u);
-	const hipError_t e = CGCK_SYNC(c->bstream);
-	burst_stop(c, 0u);
-	if (e != hipSuccess)
-		return set_err(-EIO, "cgck_test_burst_seq: drain: %s", hipGetErrorString(e));
-	for (uint32_t j = 0; j < kBurstMaxWG; j++)
-		__atomic_store_n(&c->bbox->done[j], seq, __ATOMIC_RELEASE);
-	c->bbox->req[0] = c->bbox->req[1] = 0;
-	c->breq[0] = c->breq[1] = 0;
-	if (c->bdoor) {
-		__atomic_store_n(&c->bdoor[0], 0ull, __ATOMIC_RELAXED);
-		__atomic_store_n(&c->bdoor[1], 0ull, __ATOMIC_RELAXED);
-		__builtin_ia32_sfence();
-	}
-	c->bbox->refused[0] = c->bbox->refused[1] = 0;
-	c->bseq = c->bdone = seq;
-	return burst_launch(c, seq);
-}
-
-extern "C" int cgck_test_burst_stale(cgck_ctx_t *c, uint32_t from)
-{
-	if (!c || !c->bbox || c->bslot[0] || c->bslot[1])
-		return set_err(-EINVAL, "cgck_test_burst_stale: no open server, or a request posted");
-	for (uint32_t j = from; j < kBurstMaxWG; j++)
-		__atomic_store_n(&c->bbox->done[j], c->bseq + 0x7ffffff0u, __ATOMIC_RELEASE);
-	return 0;
-}
-
-#if CGCK_LAB
-// Lab: what one host load of a BurstBox word costs while the server polls
-// (ns, mean over reps, each load after ~2 us of spin): out[0] the mailbox
-// line (stop, which the leader polls with req), out[1] refused[] (the same
-// line today), out[2] done[0], out[3] alive[0].  NULL: the thread's context.
-extern "C" int cgck_lab_box_probe(cgck_ctx_t *c, int reps, double out[4])
-{
-	if (!c)
-		c = cgck::thread_ctx_if_any();
-	if (!c || !c->bbox || reps <= 0)
-		return -EINVAL;
-	const volatile uint32_t *w[4] = {&c->bbox->stop, &c->bbox->refused[0], &c->bbox->done[0],
-					 (const volatile uint32_t *)&c->bbox->alive[0]};
-	for (int k = 0; k < 4; k++) {
-		double acc = 0;
-		uint32_t sink = 0;
-		for (int i = 0; i < reps; i++) {
-			for (const double s0 = now_s(); now_s() - s0 < 2e-6;)
-				;
-			struct timespec a, b;
-			clock_gettime(CLOCK_MONOTONIC, &a);
-			sink += *w[k];
-			__atomic_thread_fence(__ATOMIC_SEQ_CST);
-			clock_gettime(CLOCK_MONOTONIC, &b);
-			acc += (b.tv_sec - a.tv_sec) * 1e9 + (b.tv_nsec - a.tv_nsec);
-		}
-		out[k] = acc / reps + (sink == 0xdeadbeef ? 1e-9 : 0);
-	}
-	return 0;
-}
-
-// Lab: workgroup 0's timestamps of the last request (100 MHz ticks: seen,
-// block read, computed, published; then the compute phase in shader clocks)
-// and the host's view of that request (ns: post, done seen) for
-// tools/srvlat.c.
-extern "C" int cgck_lab_burst_times(cgck_ctx_t *c, uint64_t dev[5], uint64_t host[2])
-{
-	if (!c || !c->bbox)
-		return -EINVAL;
-	for (int i = 0; i < 4; i++)
-		dev[i] = __atomic_load_n(&c->bbox->lab_t[i], __ATOMIC_ACQUIRE);
-	dev[4] = __atomic_load_n(&c->bbox->lab_cyc, __ATOMIC_ACQUIRE);
-	host[0] = t_lab_host[0];
-	host[1] = t_lab_host[1];
-	return 0;
-}
-
-// Lab: thread 0's shader clocks over the last one-workgroup request's body
-// call alone (tools/srvlat's body_cycles, against tools/bodylat's).
-extern "C" uint64_t cgck_lab_burst_body(cgck_ctx_t *c)
-{
-	return c && c->bbox ? __atomic_load_n(&c->bbox->lab_body, __ATOMIC_ACQUIRE) : 0;
-}
-#endif
-
-extern "C" int cgck_burst_close(cgck_ctx_t *c)
-{
-	if (!c)
-		c = thread_ctx_if_any(); // this thread's drop-in context, if it exists
-	if (!c || !c->bbox)
-		return 0;
-	// posted requests complete first: their outputs land where their posters
-	// asked (a window still open reads them)
-	for (BurstPending *p : {c->bslot[0], c->bslot[1]})
-		if (p)
-			(void)burst_collect(c, p);
-	std::lock_guard<std::mutex> map_wr(g_map_wr); // leaves g_srv with no mapping change under way
-	{
-		std::lock_guard<std::mutex> lk(g_srv_mu);
-		for (size_t i = 0; i < g_srv.size(); i++)
-			if (g_srv[i] == c) {
-				g_srv.erase(g_srv.begin() + i);
-				break;
-			}
-	}
-	(void)hipSetDevice(c->device);
-	burst_stop(c, 1u);
-	hipError_t e = CGCK_SYNC(c->bstream); // the server sees `stop` within one poll
-	burst_release(c);
-	free_parked();
-	if (e != hipSuccess)
-		return set_err(-EIO, "cgck_burst_close: %s", hipGetErrorString(e));
-	return 0;
-}
-
 
 // --------------------------------------------------------------------------
 // Toeplitz RSS hash and the dst-cache build
@@ -1853,12 +963,8 @@ extern "C" int cgck_rss_desc_host(cgck_ctx_t *c, const void *base, size_t bytes,
 	int rc = rss_frames_check("cgck_rss_desc_host", c, base, desc, true, n, spec, res);
 	if (rc)
 		return rc;
-	for (uint64_t i = 0; i < n; i++) {
-		const uint64_t end = desc[i].frame_off + desc[i].l3_off + desc[i].ip_len;
-		if (end > bytes || end < desc[i].frame_off)
-			return set_err(-EINVAL, "cgck_rss_desc_host: descriptor %llu reaches past the %zu bytes given",
-				       (unsigned long long)i, bytes);
-	}
+	if ((rc = desc_range_check("cgck_rss_desc_host", desc, n, bytes)))
+		return rc;
 	if (n == 0)
 		return 0;
 	HIP_TRY(hipSetDevice(c->device));

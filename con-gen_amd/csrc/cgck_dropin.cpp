@@ -34,7 +34,7 @@
 using namespace cgck;
 
 #if CGCK_LAB
-extern thread_local double t_lab_post[16]; // cgck_api.cpp: the Poster's phase totals (lab, TSC ticks)
+extern thread_local double t_lab_post[16]; // cgck_burst.cpp: the Poster's phase totals (lab, TSC ticks)
 #endif
 
 namespace {
@@ -963,7 +963,7 @@ void Poster::release_if_free(int ri)
 // request).
 bool Poster::backlog(const cgck_ctx *c, int kind)
 {
-	if (!c->bbox || inflight[kind] < 0)
+	if (!c->srv.box || inflight[kind] < 0)
 		return false;
 	const PostQueue &qq = q[kind];
 	uint64_t n = 0;
@@ -975,7 +975,7 @@ bool Poster::backlog(const cgck_ctx *c, int kind)
 		n += x.n;
 		b += x.pkt_bytes;
 	}
-	return n > c->bmax || b > c->bmax_bytes;
+	return n > c->srv.max_pkts || b > c->srv.max_bytes;
 }
 
 void Poster::bound(cgck_ctx *c, int kind)
@@ -989,14 +989,14 @@ void Poster::bound(cgck_ctx *c, int kind)
 // their meta words come back too), else one request each.
 void Poster::send(cgck_ctx *c)
 {
-	const uint64_t cap_n = c->bbox ? c->bmax : UINT64_MAX;
-	const size_t cap_b = c->bbox ? c->bmax_bytes : SIZE_MAX;
+	const uint64_t cap_n = c->srv.box ? c->srv.max_pkts : UINT64_MAX;
+	const size_t cap_b = c->srv.box ? c->srv.max_bytes : SIZE_MAX;
 	Group g[2];
 	for (int k = 0; k < 2; k++)
 		if (inflight[k] < 0)
 			g[k] = gather(q[k], cap_n, cap_b);
 	// one request when both fit the server together (else one each)
-	const bool fuse = g[kRx].f && g[kTx].f && c->bbox && g[kRx].f->base == g[kTx].f->base &&
+	const bool fuse = g[kRx].f && g[kTx].f && c->srv.box && g[kRx].f->base == g[kTx].f->base &&
 			  g[kRx].f->bytes == g[kTx].f->bytes && g[kRx].n + g[kTx].n <= cap_n &&
 			  g[kRx].pb + g[kTx].pb <= cap_b;
 	for (int k = 0; k < 2; k++) {

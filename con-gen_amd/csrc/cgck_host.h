@@ -1,6 +1,7 @@
 // cgck_host.h — host-side internals shared by cgck_api.cpp (contexts,
-// batches, rings, RSS, plumbing) and cgck_dropin.cpp (the drop-in symbols and
-// the per-thread RX / TX windows).  Not part of the C-ABI.
+// batches, rings, RSS, plumbing), cgck_burst.cpp (the burst server) and
+// cgck_dropin.cpp (the drop-in symbols and the per-thread RX / TX windows).
+// Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,20 +10,8 @@
 
 #include <atomic>
 
+#include "cgck_burst.h"
 #include "cgck_internal.h"
-
-namespace cgck {
-// A request left posted on the burst server (desc_host_post): where its
-// outputs go when it is collected (burst_collect) and its result.
-struct BurstPending {
-	uint32_t seq; // 0: not pending
-	uint32_t n;
-	uint64_t range;
-	uint32_t *out, *meta;
-	uint8_t *verdict;
-	int rc;
-};
-} // namespace cgck
 
 struct cgck_ctx {
 	int device;
@@ -56,34 +45,7 @@ struct cgck_ctx {
 	// dst-cache scratch: control words + look-back status (zeroed per launch)
 	uint8_t *d_dst;
 	size_t d_dst_cap;
-	// burst server (cgck_burst_open): mailbox, request block and outputs in
-	// host-coherent pinned memory, the block's device copy in scratch
-	cgck::BurstBox *bbox; // nullptr: closed
-	uint8_t *bstage;      // request block: [BurstReq | descriptors | packet bytes]
-	size_t bstage_cap;
-	uint8_t *bstage_dev;        // device view of bstage
-	cgck::BurstBox *bbox_dev;   // device view of bbox
-	uint8_t *bresp;             // a request's outputs, packed by its n (burst_meta_off / burst_ver_off)
-	uint8_t *bresp_dev;
-	uint8_t *bscratch;          // device: the server's copy of the block (bstage_cap bytes)
-	uint64_t *brelay;           // device, uncached: the leader's relay word
-	uint32_t bmax;              // packets per request
-	size_t bmax_bytes;          // packet bytes per request (cgck_burst_open's max_bytes)
-	uint32_t bwgs;              // workgroups of the server (K)
-	uint32_t bper;              // packets per workgroup of a wide request
-	uint32_t bbad;              // bbox->bad_req as last seen
-	uint32_t bseq;              // the last request posted
-	uint32_t bdone;             // the last request known complete (a relaunch serves the ones after it)
-	cgck::BurstPending *bslot[2]; // a posted request not yet collected, per slot
-	uint32_t bbusy;             // the owner thread is inside a request (MapGuard, cgck_api.cpp)
-	// device memory the host writes through the large BAR (nullptr: none, the
-	// mailbox words are bbox->req): the two mailbox words the leader polls,
-	// then two kBurstFirst request slots for small blocks
-	uint64_t *bdoor;
-	uint8_t *bvblk;
-	bool bnext_vram;            // the block burst_slot_free handed out is a bvblk slot
-	uint64_t breq[2];           // the last mailbox word posted per slot (host copy)
-	hipStream_t bstream; // the server's own stream (it stays resident)
+	cgck::BurstServer srv; // the burst server (cgck_burst.h)
 };
 
 // Library-internal: hidden, so calls between the library's own files are
@@ -143,10 +105,6 @@ struct DescSplit {
 int desc_host_post(cgck_ctx *c, void *base, size_t bytes, const cgck_desc_t *desc, uint64_t n, uint32_t flags,
 		   uint32_t *out, uint8_t *verdict, uint32_t *meta, BurstPending *pend,
 		   const DescSummary *sum = nullptr, const DescSplit *split = nullptr);
-int burst_collect(cgck_ctx *c, BurstPending *pend);
-// Without waiting: is the posted request's every slice served (1), or not
-// yet (0)?  A request that was computed at once (seq 0) is ready.
-int burst_ready(cgck_ctx *c, const BurstPending *pend);
 
 // Staging path of one region for the drop-in symbols (burst server when open,
 // else a launch on the context stream and a synchronisation).

@@ -29,7 +29,7 @@ constexpr uint32_t kZeroBytes = 64 * 64;
 // Mailbox of the burst server (cgck_group.hip), in host-coherent pinned
 // memory.  Two request slots, so one request can be in flight while the host
 // posts the next (the pipelined RX / TX windows): request seq lives in slot
-// seq & 1 — its block at bstage + (seq & 1) * cap, its outputs at bresp +
+// seq & 1 — its block at stage + (seq & 1) * cap, its outputs at resp +
 // (seq & 1) * burst_resp_slot(max_pkts), its mailbox word req[seq & 1] =
 // seq | n << 32, stored (release) after the block.  Seqs run 1, 2, ... by
 // burst_next (never 0, parity alternating through the wrap), and the server

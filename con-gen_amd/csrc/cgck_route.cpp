@@ -1,6 +1,6 @@
 // cgck_route.cpp — the route a host-resident request takes through the burst
 // server, from the predicates of cgck_route.h that desc_host_impl /
-// cgck_burst_request (cgck_api.cpp) and burst_server_kernel (cgck_group.hip)
+// cgck_burst_request (cgck_api.cpp, cgck_burst.cpp) and burst_server_kernel (cgck_group.hip)
 // themselves call.  Host arithmetic only.  It assumes the product's settings:
 // no lab opts bits, the default caps (kServerPktsDefault, kServerCopyDefault,
 // kBurstPerWG) and a device of at least kBurstMaxWG CUs.

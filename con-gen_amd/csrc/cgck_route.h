@@ -1,5 +1,5 @@
 // cgck_route.h — which body of the burst server serves a host-resident
-// request: the constants and predicates the host (cgck_api.cpp) and the server
+// request: the constants and predicates the host (cgck_api.cpp, cgck_burst.cpp) and the server
 // kernel (cgck_group.hip) decide by, each written once here, and burst_route(),
 // which names the route from the same text.  No HIP: <stdint.h>, <stddef.h>
 // and the public header, so the whole table is tested on the CPU
