@@ -92,6 +92,28 @@ class L2Res(ctypes.Structure):
     _fields_ = [("desc_out", ctypes.c_void_p), ("cls", ctypes.c_void_p), ("count", ctypes.c_void_p)]
 
 
+# cgck_l4_desc: the class in the low nibble of cls[k], the family bit beside it,
+# the option bits of cgck_seg_t.opt, and the running counters.
+SEG_TCP, SEG_UDP, SEG_ICMP, SEG_OTHER, SEG_FRAG, SEG_NONE = 0, 1, 2, 3, 4, 5
+SEG_TCP_SHORT, SEG_TCP_BADOFF, SEG_TCP_OFFLONG, SEG_UDP_SHORT, SEG_UDP_BADLEN = 6, 7, 8, 9, 10
+SEG_NCLASS = 11
+SEG_IP6 = 1 << 4
+SEG_MSS, SEG_WS, SEG_TS, SEG_OPT_BAD = 1, 2, 4, 0x80
+SEG_NCOUNT = 12         # [class] for the eleven classes, [11] frames with SEG_IP6
+# cgck_seg_t
+SEG_DTYPE = np.dtype([("seq", "<u4"), ("ack", "<u4"), ("ts_val", "<u4"), ("ts_ecr", "<u4"),
+                      ("sport", "<u2"), ("dport", "<u2"), ("win", "<u2"), ("mss", "<u2"),
+                      ("l4_off", "<u2"), ("pay_len", "<u2"), ("th_flags", "u1"), ("hdr_len", "u1"),
+                      ("wscale", "u1"), ("opt", "u1")])
+assert SEG_DTYPE.itemsize == 32
+
+
+class L4Res(ctypes.Structure):
+    """cgck_l4_res_t: the optional outputs of the segment parser."""
+    _fields_ = [("seg", ctypes.c_void_p), ("cls", ctypes.c_void_p), ("hash", ctypes.c_void_p),
+                ("count", ctypes.c_void_p)]
+
+
 class SteerRes(ctypes.Structure):
     """cgck_steer_res_t: the optional outputs of the partition by queue id."""
     _fields_ = [("qoff", ctypes.c_void_p), ("perm", ctypes.c_void_p), ("slot", ctypes.c_void_p),
@@ -119,6 +141,7 @@ EXPORTS = (
     "cgck_test_burst_route", "cgck_test_burst_route_kind",
     "cgck_steer_work_bytes", "cgck_steer", "cgck_rss_steer_desc", "cgck_test_steer_plan",
     "cgck_l2_desc", "cgck_synth_eth", "cgck_test_l2_pass",
+    "cgck_l4_desc", "cgck_test_l4_pass",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -218,6 +241,9 @@ def bind(path):
         L.cgck_l2_desc.argtypes = [_vp, _vp, _vp, _u64, ctypes.POINTER(L2Res), _vp]
         L.cgck_synth_eth.argtypes = [_vp, _vp, _vp, _vp, _u64, _u32, _u64, _vp]
         L.cgck_test_l2_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
+    if hasattr(L, "cgck_l4_desc"):             # the segment parser (an older build loads without it)
+        L.cgck_l4_desc.argtypes = [_vp, _vp, _vp, _u64, ctypes.POINTER(L4Res), _vp]
+        L.cgck_test_l4_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
     L.cgck_dst_cache.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32, _vp, _vp]
     L.cgck_dst_cache_host.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32,
                                       ctypes.POINTER(_u32)]
@@ -717,6 +743,19 @@ class Engine:
         """cgck_test_l2_pass: frames one pass of l2d_kernel's grid covers on this device."""
         f = _u64()
         _check(load().cgck_test_l2_pass(self.ctx, ctypes.byref(f)), "cgck_test_l2_pass")
+        return f.value
+
+    def l4_desc(self, base, desc, n, seg=None, cls=None, hash=None, count=None, stream=None):
+        """cgck_l4_desc: per-frame TCP / UDP segment records of n described frames;
+        each output is optional (seg: SEG_DTYPE[n], 16-byte aligned; cls: u8[n];
+        hash: u32[n]; count: u32[SEG_NCOUNT], accumulated)."""
+        res = L4Res(seg, cls, hash, count)
+        _check(load().cgck_l4_desc(self.ctx, base, desc, n, ctypes.byref(res), stream), "cgck_l4_desc")
+
+    def l4_pass_frames(self):
+        """cgck_test_l4_pass: frames one pass of l4d_kernel's grid covers on this device."""
+        f = _u64()
+        _check(load().cgck_test_l4_pass(self.ctx, ctypes.byref(f)), "cgck_test_l4_pass")
         return f.value
 
     def synth_eth(self, base, desc, raw, n, vlan_every, seed, stream=None):

@@ -1141,6 +1141,45 @@ extern "C" int cgck_test_l2_pass(cgck_ctx_t *c, uint64_t *frames)
 	return 0;
 }
 
+// Per-frame TCP / UDP segment records (cgck_l4d.hip): one launch, no scratch.
+extern "C" int cgck_l4_desc(cgck_ctx_t *c, const void *base, const cgck_desc_t *desc, uint64_t n,
+			    const cgck_l4_res_t *res, void *stream)
+{
+	if (!c || !res || !base)
+		return set_err(-EINVAL, "cgck_l4_desc: NULL context, res or base");
+	if (n && !desc)
+		return set_err(-EINVAL, "cgck_l4_desc: NULL descriptors");
+	if (!res->seg && !res->cls && !res->hash && !res->count)
+		return set_err(-EINVAL, "cgck_l4_desc: every output is NULL");
+	if (((uintptr_t)desc & 3) != 0)
+		return set_err(-EINVAL, "cgck_l4_desc: descriptors must be 4-byte aligned");
+	if (((uintptr_t)res->seg & 15) != 0)
+		return set_err(-EINVAL, "cgck_l4_desc: seg must be 16-byte aligned");
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	L4dParams p = {};
+	p.base = (const uint8_t *)base;
+	p.desc = desc;
+	p.n = n;
+	p.zero = c->d_zero;
+	p.seg = res->seg;
+	p.cls = res->cls;
+	p.hash = res->hash;
+	p.count = res->count;
+	HIP_TRY(launch_l4d(p, c->num_cus, pick(c, stream)));
+	c->last_kernel = t_kernel;
+	return 0;
+}
+
+extern "C" int cgck_test_l4_pass(cgck_ctx_t *c, uint64_t *frames)
+{
+	if (!c || !frames)
+		return set_err(-EINVAL, "cgck_test_l4_pass: NULL argument");
+	*frames = l4d_pass_frames(c->num_cus);
+	return 0;
+}
+
 extern "C" int cgck_dst_cache(cgck_ctx_t *c, const cgck_dst_params_t *prm, cgck_dst_entry_t *out, uint32_t cap,
 			      uint32_t *count, void *stream)
 {

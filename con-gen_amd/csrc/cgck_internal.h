@@ -207,6 +207,24 @@ struct L2dParams {
 // Workgroups one launch of l2d_kernel runs at most, and frames they cover per pass.
 uint64_t l2d_pass_frames(int num_cus);
 hipError_t launch_l2d(const L2dParams &p, int num_cus, hipStream_t st);
+
+// Per-frame TCP / UDP segment records (cgck_l4d.hip; include/cgck.h, section 3).
+// desc: the burst's descriptors; `zero` = the context's zero chunk; each output
+// may be nullptr.
+struct L4dParams {
+	const uint8_t *base;
+	const void *desc;
+	uint64_t n;
+	const void *zero;
+	void *seg;
+	uint8_t *cls;
+	uint32_t *hash;
+	uint32_t *count;
+};
+
+// Workgroups one launch of l4d_kernel runs at most, and frames they cover per pass.
+uint64_t l4d_pass_frames(int num_cus);
+hipError_t launch_l4d(const L4dParams &p, int num_cus, hipStream_t st);
 hipError_t launch_rssf(const RssfParams &p, int num_cus, hipStream_t st);
 hipError_t launch_steer(const SteerParams &p, hipStream_t st);
 hipError_t launch_toeplitz(const RssParams &p, int num_cus, hipStream_t st);

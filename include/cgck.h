@@ -762,6 +762,113 @@ typedef struct cgck_l2_res {   /* device memory; each optional (NULL); at least 
 int cgck_l2_desc(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *raw, uint64_t n,
 		 const cgck_l2_res_t *res, void *stream);
 
+/* Per-frame TCP / UDP segment records: the stage after the verify.  What either
+ * stack does next with a verified frame is the front half of tcp_input / tcp_in /
+ * udp_input: the segment length rules (tcps_rcvshort, tcps_rcvbadoff, udps_hdrops,
+ * udps_badlen: bsd44/tcp_input.c:67,91-95, gbtcp/inet.c:123-131,154-156,
+ * bsd44/udp_usrreq.c:65-79), the header fields in host order (tcp_input.c:107-110;
+ * gbtcp's struct tcb, gbtcp/inet.h:128-134), the option walk (tcp_dooptions,
+ * tcp_input.c:925-996) and the PCB hash SO_HASH(faddr, lport, fport) that
+ * in_pcblookup starts from (subr.h:179-180, in_pcb.c:175).  cgck_l4_desc produces
+ * them on the device, one kernel over the burst's descriptors, so a worker reads
+ * verdict[s], cls[s] and seg[s], goes to its hash bucket, and touches a frame only
+ * when the segment carries payload.  This is header demultiplexing: the parsing
+ * ends where tcp_input.c:115 (findpcb) begins, and there is no TCP state machine
+ * here.
+ *
+ * Contract, total over every byte string.  A frame is the ip_len bytes b at base +
+ * frame_off + l3_off; ip_len bounds every read; the IP header's own length fields
+ * are not consulted (cgck_l2_desc has applied them).
+ *  1. The IP layer, by cgck_rss_desc's rules word for word, so that both calls
+ *     judge a frame alike.  ip_len == 0: NONE.  v = b[0] >> 4; CGCK_SEG_IP6 is set
+ *     whenever ip_len > 0 and v == 6, whatever the class.
+ *     v == 4: hl = (b[0] & 15) * 4; ip_len < 20, hl < 20 or ip_len < hl: NONE.
+ *       ((b[6] << 8 | b[7]) & 0x3FFF) != 0: FRAG with l4_off = hl.  That is
+ *       cgck_rss_desc's definition of a fragment, so the library has one notion of
+ *       it; ip_input.c:94 also drops a datagram with the reserved bit set, which is
+ *       not a fragment here.  Otherwise proto = b[9], l4_off = hl, F = b[12..16)
+ *       loaded little-endian.
+ *     v == 6: cgck_rss_desc's extension-header walk (no checksum-field clause).  Its
+ *       CGCK_BAD_LEN cases: NONE.  A Fragment header: FRAG with l4_off at that
+ *       header.  Otherwise proto = the terminal next-header value, l4_off where the
+ *       walk stopped, F = the XOR of the four little-endian dwords of b[8..24).
+ *     Any other v: NONE.
+ *  2. m = ip_len - l4_off; t = the bytes from l4_off on.  Every class but NONE
+ *     carries l4_off and pay_len; pay_len = m unless stated otherwise.
+ *  3. proto 6.  m < 20: TCP_SHORT.  off = (t[12] >> 4) * 4; off < 20: TCP_BADOFF;
+ *     off > m: TCP_OFFLONG (bsd44 counts both as tcps_rcvbadoff, gbtcp counts
+ *     OFFLONG as tcps_rcvshort: hence two classes).  Otherwise TCP: sport = t[0] |
+ *     t[1] << 8 and dport likewise, as stored; seq, ack and win read big-endian;
+ *     th_flags = t[13]; hdr_len = off; pay_len = m - off; and the options, with cnt
+ *     = off - 20, o = t[20..off), i = 0, while i < cnt: o[i] == 0 stops; o[i] == 1:
+ *     ++i; otherwise i + 1 >= cnt stops with OPT_BAD, len = o[i+1], len == 0 stops
+ *     with OPT_BAD, i + len > cnt stops with OPT_BAD; kind 2 with len 4 on a SYN:
+ *     mss (big-endian) and CGCK_SEG_MSS; kind 3 with len 3 on a SYN: wscale =
+ *     min(o[i+2], 14) and CGCK_SEG_WS; kind 8 with len 10: ts_val, ts_ecr and
+ *     CGCK_SEG_TS; a later occurrence overwrites an earlier one; i += len (a len of
+ *     1 advances one byte, as the reference does).  On every well-formed segment
+ *     this is tcp_dooptions.  It differs where the reference reads cp[1] or option
+ *     data past the option area, for which it has no bound (tcp_input.c:937-948):
+ *     here no byte at or past `off` is ever consulted.
+ *  4. proto 17.  m < 8: UDP_SHORT.  ulen = t[4] << 8 | t[5]; ulen > m or ulen < 8:
+ *     UDP_BADLEN.  The first condition is udps_badlen; the second has no
+ *     counterpart: the reference goes on with a datagram shorter than its header.
+ *     Otherwise UDP: the ports, hdr_len = 8, pay_len = ulen - 8.
+ *  5. proto 1 under v4, or 58 under v6: ICMP.  Anything else: OTHER.  Both carry
+ *     only l4_off and pay_len.
+ *  6. hash[k] = F ^ (F >> 16) ^ bswap16(dport ^ sport) for TCP and UDP: SO_HASH(ip_src,
+ *     dport, sport) as the receiver's in_pcblookup computes it; for IPv4 it equals
+ *     the `hash` of the cgck_dst_entry_t the frame answers.  0 for every other class.
+ *  7. count[class] += 1 per frame; count[11] += 1 per frame with CGCK_SEG_IP6.
+ *
+ * Execution.  Asynchronous on `stream` (NULL: the context's).  n == 0 returns 0,
+ * launches nothing and writes nothing.  The frames and `desc` are never written.
+ * The library keeps no scratch for this call.  One kernel, l4d_kernel; `desc` is
+ * any 4-byte aligned array, and every read lies inside the 16-byte granules that
+ * hold a byte of [frame, frame + ip_len) (cgck_rss_desc's rule).
+ * Measured (DESIGN.md §5.12, 16M dual-stack IMIX frames in 2048-byte slots on one
+ * MI355X, random TCP header bytes: a worst case for the option walk): 0.62 ms
+ * with all four outputs, 0.61 ms with seg alone and 0.53 ms with cls and count,
+ * against 0.50 ms for cgck_rss_desc (hash only) on the same descriptors in the
+ * same run: 1.23, 1.21 and 1.05 times the hash, with margins of 5 to 14 % between
+ * allocations; the excess is the 37 bytes written per frame.
+ * There is no host form and no strided form: a host burst's header lines are in
+ * the host's caches for the RX window anyway, where this parse costs less than a
+ * launch; and the call follows cgck_l2_desc or cgck_steer, which both leave a
+ * descriptor array.
+ * -EINVAL: a NULL ctx, res or base, or (with n > 0) a NULL desc; every output
+ * NULL; a misaligned desc; a seg that is not 16-byte aligned. */
+typedef struct cgck_seg {      /* 32 bytes; fields a class does not name are 0 */
+	uint32_t seq, ack;         /* host order (tcp_input.c:107-108) */
+	uint32_t ts_val, ts_ecr;   /* host order; valid with CGCK_SEG_TS */
+	uint16_t sport, dport;     /* as stored: the u16 a little-endian load of the two bytes gives
+	                              (be16_t, as in_pcb.c:178-182 compares them) */
+	uint16_t win;              /* host order, unscaled */
+	uint16_t mss;              /* host order; valid with CGCK_SEG_MSS */
+	uint16_t l4_off;           /* from the IP header's first byte */
+	uint16_t pay_len;
+	uint8_t th_flags;
+	uint8_t hdr_len;           /* TCP: th_off * 4 (20..60); UDP: 8; else 0 */
+	uint8_t wscale;            /* min(value, 14) (TCP_MAX_WINSHIFT); valid with CGCK_SEG_WS */
+	uint8_t opt;               /* CGCK_SEG_MSS | _WS | _TS | _OPT_BAD */
+} cgck_seg_t;
+enum { CGCK_SEG_TCP = 0, CGCK_SEG_UDP = 1, CGCK_SEG_ICMP = 2, CGCK_SEG_OTHER = 3, CGCK_SEG_FRAG = 4,
+       CGCK_SEG_NONE = 5, CGCK_SEG_TCP_SHORT = 6, CGCK_SEG_TCP_BADOFF = 7, CGCK_SEG_TCP_OFFLONG = 8,
+       CGCK_SEG_UDP_SHORT = 9, CGCK_SEG_UDP_BADLEN = 10, CGCK_SEG_NCLASS = 11 };   /* low nibble of cls[k] */
+enum { CGCK_SEG_IP6 = 1u << 4 };                                                  /* flag bit of cls[k] */
+enum { CGCK_SEG_MSS = 1, CGCK_SEG_WS = 2, CGCK_SEG_TS = 4, CGCK_SEG_OPT_BAD = 0x80 };
+#define CGCK_SEG_NCOUNT 12     /* [class] for the eleven classes, [11] frames with CGCK_SEG_IP6 */
+
+typedef struct cgck_l4_res {   /* device memory; each optional (NULL); at least one non-NULL */
+	cgck_seg_t *seg;           /* [n], 16-byte aligned */
+	uint8_t *cls;              /* [n] */
+	uint32_t *hash;            /* [n] */
+	uint32_t *count;           /* u32[CGCK_SEG_NCOUNT], running counters (+=) */
+} cgck_l4_res_t;
+
+int cgck_l4_desc(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *desc, uint64_t n,
+		 const cgck_l4_res_t *res, void *stream);
+
 /* One dst-cache entry: the fields thread_init_dst_cache fills in struct
  * ip_socket (con-gen.c:344-349; subr.h:218-228).  16 bytes. */
 typedef struct cgck_dst_entry {
@@ -860,6 +967,8 @@ int cgck_test_steer_plan(uint64_t n, uint32_t queue_num, uint32_t *tile, uint32_
  * workgroup cap (four per compute unit) x 256.  A burst above twice that makes
  * every wave run three steps.  -EINVAL: a NULL ctx or frames. */
 int cgck_test_l2_pass(cgck_ctx_t *ctx, uint64_t *frames);
+/* The same for cgck_l4_desc's grid. */
+int cgck_test_l4_pass(cgck_ctx_t *ctx, uint64_t *frames);
 
 #ifdef __cplusplus
 }
