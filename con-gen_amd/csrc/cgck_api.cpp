@@ -1137,7 +1137,7 @@ extern "C" int cgck_test_l2_pass(cgck_ctx_t *c, uint64_t *frames)
 {
 	if (!c || !frames)
 		return set_err(-EINVAL, "cgck_test_l2_pass: NULL argument");
-	*frames = l2d_pass_frames(c->num_cus);
+	*frames = frame_pass_frames(c->num_cus);
 	return 0;
 }
 
@@ -1176,7 +1176,7 @@ extern "C" int cgck_test_l4_pass(cgck_ctx_t *c, uint64_t *frames)
 {
 	if (!c || !frames)
 		return set_err(-EINVAL, "cgck_test_l4_pass: NULL argument");
-	*frames = l4d_pass_frames(c->num_cus);
+	*frames = frame_pass_frames(c->num_cus);
 	return 0;
 }
 

@@ -204,8 +204,6 @@ struct L2dParams {
 	uint32_t *count;
 };
 
-// Workgroups one launch of l2d_kernel runs at most, and frames they cover per pass.
-uint64_t l2d_pass_frames(int num_cus);
 hipError_t launch_l2d(const L2dParams &p, int num_cus, hipStream_t st);
 
 // Per-frame TCP / UDP segment records (cgck_l4d.hip; include/cgck.h, section 3).
@@ -222,8 +220,9 @@ struct L4dParams {
 	uint32_t *count;
 };
 
-// Workgroups one launch of l4d_kernel runs at most, and frames they cover per pass.
-uint64_t l4d_pass_frames(int num_cus);
+// Frames that the workgroups one launch of rssf_kernel, l2d_kernel or l4d_kernel
+// runs at most cover per pass (cgck_frame.h).
+uint64_t frame_pass_frames(int num_cus);
 hipError_t launch_l4d(const L4dParams &p, int num_cus, hipStream_t st);
 hipError_t launch_rssf(const RssfParams &p, int num_cus, hipStream_t st);
 hipError_t launch_steer(const SteerParams &p, hipStream_t st);

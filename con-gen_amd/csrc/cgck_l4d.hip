@@ -5,20 +5,12 @@
 // host order, the option walk and the PCB hash, so that a worker goes from a
 // descriptor to its hash bucket without reading the frame.
 //
-// Shape.  rssf_kernel's (cgck_rssf.hip): one lane per frame, 64 frames per
-// wave-step, waves grid-stride over the steps, the descriptors of step s + 2 and
-// the chunks of step s + 1 loaded before step s is judged.
-//
-// Memory.  Six aligned 16-byte chunks from the frame's first granule on, loaded
-// unconditionally and realigned in registers (v_bfi by the dword shift,
-// v_alignbyte by the byte shift), give the frame-relative bytes [0, 80) at any
-// start alignment: an IPv4 header without options and a whole 60-byte TCP header,
-// or an IPv6 header and a TCP header with timestamps (72).  In a 2048-byte ring
-// slot the six chunks lie in the frame's first 128-byte line, so they cost no
-// more memory traffic than rssf's four.  Chunk indices are clamped to the
-// granules that hold a byte of [frame, frame + ip_len); a lane without a frame
-// reads the zero chunk.  A byte past ip_len may come back as anything: every rule
-// compares a length before it consults a byte.
+// Shape and memory are cgck_frame.h's, with six chunks a frame: they give the
+// frame-relative bytes [0, 80) at any start alignment, an IPv4 header without
+// options and a whole 60-byte TCP header, or an IPv6 header and a TCP header
+// with timestamps (72).  In a 2048-byte ring slot the six chunks lie in the
+// frame's first 128-byte line, so they cost no more memory traffic than rssf's
+// four.
 //
 // Window.  The transport header starts at a lane-variant offset and the option
 // walk indexes bytes at a lane-variant position; a register array indexed that
@@ -34,124 +26,27 @@
 // the lane's row, only in the lanes that need it, behind a wave-wide __any; the
 // headers of an IPv6 extension chain likewise, as rssf walks them.
 //
-// Stores.  A wave-step's 64 records are 2 KiB consecutive.  Each lane puts its
-// two 16-byte halves into the wave's LDS block and the wave stores the block as
-// two instructions of 64 consecutive 16-byte pieces (l2d's finding, DESIGN.md
-// §5.11: stores at a lane stride cost 8 % there).  Plain vector stores.
+// Stores.  A wave-step's 64 records are 2 KiB consecutive, two 16-byte halves a
+// lane through wave_turn_store (l2d's finding, DESIGN.md §5.11: stores at a lane
+// stride cost 8 % there).
 //
-// 21 KiB of rows, 8 KiB of record blocks and 48 bytes of counters per 256-thread
-// workgroup: four workgroups per CU, as rssf and l2d run.  Counters go through an
-// LDS histogram (ds_add), and each workgroup adds its non-zero bins to global
-// memory once.
-//
-// The chunk helpers are private copies of rssf's, so that rssf_kernel's device
-// code does not depend on this unit.
-#include "cgck_device.h"
+// LDS.  21 KiB of rows, 8 KiB of turned records and 48 bytes of counters per
+// workgroup.
+#include "cgck_frame.h"
 
 namespace cgck {
 
-constexpr int kL4dThreads = 256;
-constexpr int kL4dWaves = kL4dThreads / 64;
-constexpr int kL4dWgPerCu = 4;
 constexpr uint32_t kL4dBins = CGCK_SEG_NCOUNT;
 constexpr int kL4dChunks = 6;                        // first round: bytes [0, 80)
 constexpr uint32_t kL4dWin = 16u * kL4dChunks - 16u; // 80
 constexpr int kL4dChunks2 = 5;                       // second round: bytes [l4_off, l4_off + 64)
 constexpr int kL4dRow = 21;                          // dwords per lane: 80 bytes, odd stride
-constexpr int kL4dMaxExt = kV6MaxExt;
-
-struct SDesc {
-	uint32_t lo, hi, w2;
-};
-
-struct SChunks {
-	u32x4_t c[kL4dChunks];
-};
-
-// Descriptor of frame k (index clamped: the lanes past n of the last step
-// re-read the last descriptor and drop it in l4d_frame).
-__device__ __forceinline__ SDesc l4d_desc(const L4dParams &p, uint64_t k)
-{
-	const uint64_t kk = k < p.n ? k : p.n - 1;
-	const CGCK_GLOBAL uint32_t *g = (const CGCK_GLOBAL uint32_t *)p.desc + 3 * kk;
-	SDesc d;
-	d.lo = g[0];
-	d.hi = g[1];
-	d.w2 = g[2];
-	return d;
-}
-
-__device__ __forceinline__ void l4d_frame(const L4dParams &p, const SDesc &d, uint64_t k, uint64_t &a0, uint32_t &len)
-{
-	a0 = reinterpret_cast<uint64_t>(p.base) + (((uint64_t)d.hi << 32) | d.lo) + (d.w2 & 0xffffu);
-	len = k < p.n ? d.w2 >> 16 : 0;
-}
-
-// Granules that hold a byte of [a0, a0 + len).
-__device__ __forceinline__ int l4d_granules(uint64_t a0, uint32_t len)
-{
-	return len ? (int)(((uint32_t)(a0 & 15) + len + 15) >> 4) : 0;
-}
-
-// The first six granules of the frame, clamped to its last; the zero chunk for a
-// lane without a byte.
-__device__ __forceinline__ SChunks l4d_first(uint64_t a0, uint32_t len, const void *zero, int lane)
-{
-	const int nch = l4d_granules(a0, len);
-	SChunks r;
-#pragma unroll
-	for (int i = 0; i < kL4dChunks; ++i) {
-		const uint64_t at = nch > 0 ? (a0 & ~(uint64_t)15) + 16u * (uint32_t)min(i, nch - 1)
-					    : reinterpret_cast<uint64_t>(zero) + 64u * (uint32_t)lane;
-		r.c[i] = *gbl_at<const u32x4_t>(at);
-	}
-	return r;
-}
-
-// NC chunks whose first holds byte q (0..15) of the run wanted: the 4 NC - 4
-// dwords from that byte on, into the lane's row.
-template <int NC>
-__device__ __forceinline__ void l4d_realign(const u32x4_t (&c)[NC], uint32_t q, uint32_t (&R)[4 * NC - 4])
-{
-	uint32_t D[4 * NC];
-#pragma unroll
-	for (int i = 0; i < NC; ++i) {
-		D[4 * i + 0] = c[i][0];
-		D[4 * i + 1] = c[i][1];
-		D[4 * i + 2] = c[i][2];
-		D[4 * i + 3] = c[i][3];
-	}
-	const uint32_t m1 = opaque((q & 4) ? ~0u : 0u), m2 = opaque((q & 8) ? ~0u : 0u);
-	uint32_t S[4 * NC - 3];
-#pragma unroll
-	for (int i = 0; i < 4 * NC - 3; ++i)
-		S[i] = pick(m2, pick(m1, D[i + 3], D[i + 2]), pick(m1, D[i + 1], D[i]));
-#pragma unroll
-	for (int i = 0; i < 4 * NC - 4; ++i)
-		R[i] = __builtin_amdgcn_alignbyte(S[i + 1], S[i], q & 3u);
-}
-
-// The frame-relative dword at byte `off` (a multiple of 4, off + 2 <= len): the
-// one or two granules that hold it, realigned (rssf_dword_at's rule).
-__device__ __forceinline__ uint32_t l4d_dword_at(uint64_t a0, uint32_t len, uint32_t off)
-{
-	const int nch = l4d_granules(a0, len);
-	const uint32_t at = (uint32_t)(a0 & 15) + off;
-	const int j = (int)(at >> 4);
-	const uint64_t A = a0 & ~(uint64_t)15;
-	const u32x4_t x = *gbl_at<const u32x4_t>(A + 16u * (uint32_t)min(j, nch - 1));
-	const u32x4_t y = *gbl_at<const u32x4_t>(A + 16u * (uint32_t)min(j + 1, nch - 1));
-	const uint32_t dq = (at >> 2) & 3u;
-	const uint32_t lo = dq == 0 ? x[0] : dq == 1 ? x[1] : dq == 2 ? x[2] : x[3];
-	const uint32_t hi = dq == 0 ? x[1] : dq == 1 ? x[2] : dq == 2 ? x[3] : y[0];
-	return __builtin_amdgcn_alignbyte(hi, lo, at & 3u);
-}
 
 // The 64 bytes from frame byte `off` on (off < len) into the lane's row: the five
 // granules from the one that holds it, clamped to the frame's last.
 __device__ __forceinline__ void l4d_second(uint64_t a0, uint32_t len, uint32_t off, uint32_t *row)
 {
-	const int nch = l4d_granules(a0, len);
+	const int nch = frame_granules(a0, len);
 	const uint32_t at = (uint32_t)(a0 & 15) + off;
 	const int j = (int)(at >> 4);
 	const uint64_t A = a0 & ~(uint64_t)15;
@@ -160,61 +55,40 @@ __device__ __forceinline__ void l4d_second(uint64_t a0, uint32_t len, uint32_t o
 	for (int i = 0; i < kL4dChunks2; ++i)
 		c[i] = *gbl_at<const u32x4_t>(A + 16u * (uint32_t)min(j + i, nch - 1));
 	uint32_t R[4 * kL4dChunks2 - 4];
-	l4d_realign<kL4dChunks2>(c, at & 15u, R);
+	frame_realign(c, at & 15u, R);
 #pragma unroll
 	for (int i = 0; i < 4 * kL4dChunks2 - 4; ++i)
 		row[i] = R[i];
 }
 
-__device__ __forceinline__ uint32_t l4d_be16(uint32_t w)
-{
-	return ((w & 255u) << 8) | ((w >> 8) & 255u);
-}
-
 // SG: seg is written (the fields and the option walk); X: cls, hash and / or the
 // counters.
 template <bool SG, bool X>
-__global__ __launch_bounds__(kL4dThreads) void l4d_kernel(L4dParams p)
+__global__ __launch_bounds__(kFrameThreads) void l4d_kernel(L4dParams p)
 {
 	__shared__ uint32_t hist[kL4dBins];
-	__shared__ uint32_t rows[kL4dThreads * kL4dRow];
-	__shared__ __attribute__((aligned(16))) u32x4_t xpose[SG ? kL4dWaves : 1][128]; // a wave-step's records on their way out
+	__shared__ uint32_t rows[kFrameThreads * kL4dRow];
+	__shared__ __attribute__((aligned(16))) u32x4_t xpose[SG ? kFrameWaves : 1][128]; // a wave-step's records on their way out
 	const bool count = X && p.count != nullptr;
 	if (X) {
-		if (threadIdx.x < kL4dBins)
-			hist[threadIdx.x] = 0;
+		frame_hist_zero(hist, kL4dBins);
 		__syncthreads();
 	}
 
-	const int lane = threadIdx.x & 63;
 	uint32_t *row = rows + kL4dRow * threadIdx.x;
 	const uint8_t *rowb = reinterpret_cast<const uint8_t *>(row);
-	const uint64_t nsteps = (p.n + 63) / 64;
-	const uint64_t W = (uint64_t)gridDim.x * kL4dWaves;
-	uint64_t s = (uint64_t)blockIdx.x * kL4dWaves + (threadIdx.x >> 6);
+	const FrameDescs frames = {p.base, p.desc, p.n};
+	FrameCursor<kL4dChunks, FrameDescs> cur(frames, p.n, p.zero);
 
-	if (s < nsteps) {
-		// step s: descriptor and chunks; step s + W: descriptor
-		const SDesc dc = l4d_desc(p, s * 64 + lane);
-		uint64_t a0;
-		uint32_t len;
-		l4d_frame(p, dc, s * 64 + lane, a0, len);
-		SChunks cc = l4d_first(a0, len, p.zero, lane);
-		SDesc dn = l4d_desc(p, (s + W) * 64 + lane);
-		for (; s < nsteps; s += W) {
-			// step s + W's chunks and step s + 2W's descriptor go out before
-			// step s is judged (past the end: no frame, the zero chunk)
-			uint64_t a0n;
-			uint32_t lenn;
-			l4d_frame(p, dn, (s + W) * 64 + lane, a0n, lenn);
-			const SChunks cn = l4d_first(a0n, lenn, p.zero, lane);
-			const SDesc dn2 = l4d_desc(p, (s + 2 * W) * 64 + lane);
-
-			const uint64_t k = s * 64 + lane;
+	if (cur.more()) {
+		for (cur.start(); cur.more(); cur.advance()) {
+			cur.ahead();
+			const uint64_t a0 = cur.a0, k = cur.k();
+			const uint32_t len = cur.len;
 			const bool ok = k < p.n;
 			// frame-relative dwords R0 .. R19 = bytes [0, 80)
 			uint32_t R[4 * kL4dChunks - 4];
-			l4d_realign<kL4dChunks>(cc.c, (uint32_t)(a0 & 15), R);
+			frame_realign(cur.c.c, (uint32_t)(a0 & 15), R);
 
 			// step 1, the IP layer (rssf's rules): st 0 NONE, 1 FRAG, 2 proto known
 			const uint32_t b0 = R[0] & 255u, v = b0 >> 4;
@@ -246,29 +120,30 @@ __global__ __launch_bounds__(kL4dThreads) void l4d_kernel(L4dParams p)
 			for (;;) {
 				bool ext = false;
 				if (walk) {
-					if (off > len) {
-						walk = false;
-					} else if (nh == 44) {
+					switch (v6_next(off, len, nh, seen)) {
+					case kV6Past:
+					case kV6Cut:
+						break; // st stays 0
+					case kV6Frag:
 						st = 1;
-						walk = false;
-					} else if (!v6_is_ext(nh)) {
+						break;
+					case kV6Upper:
 						st = 2;
 						proto = nh;
-						walk = false;
-					} else if (seen == (uint32_t)kL4dMaxExt || off + 2 > len) {
-						walk = false;
-					} else {
+						break;
+					case kV6More:
 						ext = true;
+						break;
 					}
+					walk = ext;
 				}
 				if (!__any(ext))
 					break;
 				if (ext) {
-					const uint32_t w = l4d_dword_at(a0, len, off);
-					const uint32_t hlen = (w >> 8) & 255u;
-					off += nh == 51 ? (hlen + 2) * 4 : (hlen + 1) * 8;
-					nh = w & 255u;
-					++seen;
+					const V6At nx = v6_eat(frame_dword_at(a0, len, off), off, nh, seen);
+					off = nx.off;
+					nh = nx.nh;
+					seen = nx.seen;
 				}
 			}
 
@@ -327,7 +202,7 @@ __global__ __launch_bounds__(kL4dThreads) void l4d_kernel(L4dParams p)
 						if (SG) {
 							seq = __builtin_bswap32(t[1]);
 							ack = __builtin_bswap32(t[2]);
-							win = l4d_be16(w3 >> 16);
+							win = bswap16(w3 >> 16);
 							hdr = th;
 							// tcp_dooptions (tcp_input.c:925-996) over o[0, cnt): no
 							// byte at or past th is consulted
@@ -375,7 +250,7 @@ __global__ __launch_bounds__(kL4dThreads) void l4d_kernel(L4dParams p)
 					cls = CGCK_SEG_UDP_SHORT;
 				} else {
 					const uint32_t *t = row + (rb >> 2);
-					const uint32_t ulen = l4d_be16(t[1]);
+					const uint32_t ulen = bswap16(t[1]);
 					if (ulen > m || ulen < 8) {
 						cls = CGCK_SEG_UDP_BADLEN;
 					} else {
@@ -391,26 +266,13 @@ __global__ __launch_bounds__(kL4dThreads) void l4d_kernel(L4dParams p)
 			const bool l4 = cls == CGCK_SEG_TCP || cls == CGCK_SEG_UDP;
 
 			if (SG) {
-				// The step's 64 records are 128 consecutive 16-byte pieces: turned
-				// through the wave's LDS block they go out as two stores of 64
-				// consecutive pieces instead of two at a 32-byte stride.
-				u32x4_t *xs = xpose[threadIdx.x >> 6];
-				const u32x4_t lo = {seq, ack, tsv, tse};
-				const u32x4_t hi = {ports, win | (mss << 16), off | (pay << 16),
-						    cls == CGCK_SEG_TCP ? thf | (hdr << 8) | (wsc << 16) | (opt << 24) : hdr << 8};
-				xs[2 * lane + 0] = lo;
-				xs[2 * lane + 1] = hi;
-				__builtin_amdgcn_wave_barrier();
-				asm volatile("" ::: "memory");
-				const uint64_t left = p.n - s * 64;
-				const uint32_t nv = 2 * (uint32_t)(left < 64 ? left : 64);
-				CGCK_GLOBAL u32x4_t *g = (CGCK_GLOBAL u32x4_t *)p.seg + 128 * s;
-#pragma unroll
-				for (int j = 0; j < 2; ++j)
-					if ((uint32_t)(64 * j + lane) < nv)
-						g[64 * j + lane] = xs[64 * j + lane];
-				__builtin_amdgcn_wave_barrier();
-				asm volatile("" ::: "memory");
+				// 128 consecutive 16-byte pieces a step
+				const u32x4_t mine[2] = {
+					{seq, ack, tsv, tse},
+					{ports, win | (mss << 16), off | (pay << 16),
+					 cls == CGCK_SEG_TCP ? thf | (hdr << 8) | (wsc << 16) | (opt << 24) : hdr << 8}};
+				wave_turn_store(xpose[threadIdx.x >> 6], mine, (CGCK_GLOBAL u32x4_t *)p.seg + 128 * cur.s,
+						p.n - cur.s * 64, cur.lane);
 			}
 			if (X && ok) {
 				if (p.cls)
@@ -427,37 +289,17 @@ __global__ __launch_bounds__(kL4dThreads) void l4d_kernel(L4dParams p)
 						__hip_atomic_fetch_add(hist + 11, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 				}
 			}
-
-			dn = dn2;
-			cc = cn;
-			a0 = a0n;
-			len = lenn;
 		}
 	}
-	if (X) {
-		__syncthreads();
-		if (count && threadIdx.x < kL4dBins) {
-			const uint32_t cnt = hist[threadIdx.x];
-			if (cnt)
-				__hip_atomic_fetch_add((CGCK_GLOBAL uint32_t *)p.count + threadIdx.x, cnt, __ATOMIC_RELAXED,
-						       __HIP_MEMORY_SCOPE_AGENT);
-		}
-	}
-}
-
-uint64_t l4d_pass_frames(int num_cus)
-{
-	return (uint64_t)num_cus * kL4dWgPerCu * kL4dThreads;
+	if (X)
+		frame_hist_flush(hist, kL4dBins, p.count);
 }
 
 hipError_t launch_l4d(const L4dParams &p, int num_cus, hipStream_t st)
 {
 	if (p.n == 0)
 		return hipSuccess;
-	const uint64_t steps = (p.n + 63) / 64;
-	const uint64_t want = (steps + kL4dWaves - 1) / kL4dWaves;
-	const uint64_t cap = (uint64_t)num_cus * kL4dWgPerCu;
-	const dim3 g((unsigned)(want < cap ? want : cap)), b(kL4dThreads);
+	const dim3 g(frame_grid(p.n, num_cus)), b(kFrameThreads);
 	const bool sg = p.seg != nullptr, x = p.cls != nullptr || p.hash != nullptr || p.count != nullptr;
 #define CGCK_L4D(Ss, Xx)                                                          \
 	do {                                                                      \

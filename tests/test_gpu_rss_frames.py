@@ -221,6 +221,100 @@ def test_many_workgroups(engine, port, key):
         b.free()
 
 
+SLOT, SLOT_L3 = 128, 14                 # three-pass burst: a frame at byte 14 of its 128-byte slot
+PERIOD = 64 * 15                        # whole steps, and no divisor of a pass (a power of two)
+CAN, CANARY = 64, 0xC3
+
+
+@pytest.fixture(scope="module")
+def slot_period(port, key):
+    """One period of the three-pass burst: class and fuzz frames that fit a slot,
+    laid out, with the referee's full hash and kind under TCP | UDP."""
+    rng = np.random.default_rng(1000)
+    frames = [f for f in RB.fuzz(rng, 800) + RB.all_classes(rng) + RB.fuzz(rng, 800) if len(f) <= SLOT - SLOT_L3]
+    assert len(frames) >= PERIOD
+    frames = frames[:PERIOD]
+    buf, desc, offs, lens = RB.slotted(rng, frames, SLOT, SLOT_L3)
+    buf = np.ascontiguousarray(buf[:PERIOD * SLOT])            # slotted()'s tail past the last slot is not part of it
+    assert np.all((offs & 15) == SLOT_L3) and int((offs + lens).max()) <= buf.nbytes
+    h, kind = rssref.expect(port, buf, offs, lens, key, TCP | UDP)[:2]
+    return frames, buf, desc, h, kind
+
+
+def test_three_passes(engine, key, slot_period):
+    """Above twice what one pass of the grid covers, plus a step and a frame: every
+    wave runs three steps, so both prefetch depths carry real frames and run dry
+    (the zero chunk past the end).  The period does not divide a pass, so the
+    steps of one wave hold different frames."""
+    frames, pbuf, pdesc, h, kind = slot_period
+    ok = rssref.hashed(kind)
+    assert np.count_nonzero(ok) >= 0.6 * PERIOD
+    L4, IP6 = rssref.RSS_L4, rssref.RSS_IP6
+    opts4 = [i for i, f in enumerate(frames) if len(f) and f[0] >> 4 == 4 and f[0] & 15 > 5 and kind[i] == L4]
+    chain6 = [i for i, f in enumerate(frames) if kind[i] == IP6 | L4 and rssref.walk6(f, len(f))[0] > 40]
+    frag = [i for i, f in enumerate(frames) if ok[i] and RB.tags(f) & {"v4_mf", "v4_off", "v6_frag_direct", "v6_frag_chain"}]
+    assert opts4 and chain6 and frag, "IPv4 options before the ports, an IPv6 chain before them, a fragment"
+    qn = 5
+    queue = np.where(ok, h % qn, rssref.NO_QUEUE).astype(np.uint8)
+
+    per_pass = engine.l2_pass_frames()
+    assert per_pass % 256 == 0 and per_pass >= 1024 and per_pass % PERIOD != 0 and (2 * per_pass) % PERIOD != 0
+    n = 2 * per_pass + 65
+    assert n * SLOT < 128_000_000
+    reps = (1 << 20) // (PERIOD * SLOT)                # periods a piece: under 1 MiB of frame bytes
+    piece = reps * PERIOD
+    # Frames and descriptors go up and the results come down a piece at a time:
+    # the host never holds an array of the whole burst.
+    L, st = cgck.load(), engine.stream
+    sizes = {"frames": SLOT * n, "desc": 12 * n, "hash": 4 * n, "kind": n, "queue": n, "qcount": 4 * 128}
+    dev = {x: cgck.DeviceBuffer(2 * CAN + sz) for x, sz in sizes.items()}
+    try:
+        for x, d in dev.items():
+            assert L.cgck_memset(d.ptr, CANARY, 2 * CAN + sizes[x], st) == 0
+            assert L.cgck_memset(d.ptr + CAN, 0xEE, sizes[x], st) == 0
+        dev["qcount"].upload(SEED, off=CAN, stream=st)
+        fpiece, dpiece = np.tile(pbuf, reps), np.tile(pdesc, reps)
+        dpiece["frame_off"] += np.repeat(np.arange(reps, dtype=np.uint64) * np.uint64(PERIOD * SLOT), PERIOD)
+        for a in range(0, n, piece):
+            k = min(piece, n - a)
+            d = dpiece[:k].copy()
+            d["frame_off"] += np.uint64(SLOT * a)
+            dev["frames"].upload(fpiece[:SLOT * k], off=CAN + SLOT * a, stream=st)
+            dev["desc"].upload(d, off=CAN + 12 * a, stream=st)
+        engine.sync()
+        base = dev["frames"].ptr + CAN
+        assert base % 16 == 0
+        engine.rss_desc(base, dev["desc"].ptr + CAN, n, cgck.Engine.rss_spec(key, FULL, TCP | UDP, qn),
+                        **{x: dev[x].ptr + CAN for x in ALL})
+        assert engine.last_kernel == "rssf_kernel<true, true>", engine.last_kernel
+
+        def fetch(x, off, count, dtype):
+            got = np.zeros(count, dtype)
+            dev[x].download(got, off=off, stream=st)
+            engine.sync()
+            return got
+
+        eh, ek, eq = np.tile(h, reps), np.tile(kind, reps), np.tile(queue, reps)
+        for a in range(0, n, piece):
+            k = min(piece, n - a)
+            same(fetch("hash", CAN + 4 * a, k, np.uint32), eh[:k], f"hash, frames {a} ..")
+            same(fetch("kind", CAN + a, k, np.uint8), ek[:k], f"kind, frames {a} ..")
+            same(fetch("queue", CAN + a, k, np.uint8), eq[:k], f"queue, frames {a} ..")
+            same(fetch("frames", CAN + SLOT * a, SLOT * k, np.uint8), fpiece[:SLOT * k], f"frame bytes, frames {a} ..")
+            gd = fetch("desc", CAN + 12 * a, k, cgck.DESC_DTYPE)
+            assert np.array_equal(gd["ip_len"], dpiece["ip_len"][:k]) and int(gd["frame_off"][k - 1]) == SLOT * (a + k - 1)
+        want = SEED.copy()
+        want[:qn] += ((n // PERIOD) * np.bincount(queue[ok], minlength=qn)
+                      + np.bincount(queue[:n % PERIOD][ok[:n % PERIOD]], minlength=qn)).astype(np.uint32)
+        same(fetch("qcount", CAN, 128, np.uint32), want, "qcount")
+        for x, d in dev.items():
+            for off in (0, CAN + sizes[x]):
+                assert np.all(fetch(x, off, CAN, np.uint8) == CANARY), f"{x}: bytes outside the array were written"
+    finally:
+        for d in dev.values():
+            d.free()
+
+
 # -- 4. the strided form --------------------------------------------------------------
 
 @pytest.mark.parametrize("stride,l3", [(64, 0), (64, 14), (2048, 0), (2048, 14)])
