@@ -114,6 +114,32 @@ class L4Res(ctypes.Structure):
                 ("count", ctypes.c_void_p)]
 
 
+# cgck_l4_build: the flow record, the flag bits of cgck_flow_t.flags, the class in
+# the low nibble of cls[k] with the flag bits beside it, and the running counters.
+FLOW_DTYPE = np.dtype([("eth_dst", "u1", (6,)), ("eth_src", "u1", (6,)), ("vlan_tci", "<u2"), ("flags", "u1"),
+                       ("ttl", "u1"), ("laddr", "u1", (16,)), ("faddr", "u1", (16,))])
+assert FLOW_DTYPE.itemsize == 48
+FLOW_IP6, FLOW_VLAN = 1, 2
+BLD_TCP, BLD_UDP, BLD_SKIP, BLD_BADFLOW, BLD_BADSEG, BLD_NOROOM = 0, 1, 2, 3, 4, 5
+BLD_NCLASS = 6
+BLD_IP6 = 1 << 4
+BLD_PAYLOAD = 1 << 5
+BLD_NCOUNT = 8          # [class] for the six classes, [6] built IPv6 frames, [7] built frames with BLD_PAYLOAD
+
+
+class L4BuildIn(ctypes.Structure):
+    """cgck_l4_build_in_t: where the frames go and what they are built from."""
+    _fields_ = [("slot", ctypes.c_void_p), ("seg", ctypes.c_void_p), ("cls", ctypes.c_void_p),
+                ("flow", ctypes.c_void_p), ("fidx", ctypes.c_void_p), ("nflow", ctypes.c_uint32),
+                ("ip_id0", ctypes.c_uint16), ("ip_off", ctypes.c_uint16)]
+
+
+class L4BuildRes(ctypes.Structure):
+    """cgck_l4_build_res_t: the optional outputs of the frame builder."""
+    _fields_ = [("raw_out", ctypes.c_void_p), ("desc_out", ctypes.c_void_p), ("cls", ctypes.c_void_p),
+                ("count", ctypes.c_void_p)]
+
+
 class SteerRes(ctypes.Structure):
     """cgck_steer_res_t: the optional outputs of the partition by queue id."""
     _fields_ = [("qoff", ctypes.c_void_p), ("perm", ctypes.c_void_p), ("slot", ctypes.c_void_p),
@@ -142,6 +168,7 @@ EXPORTS = (
     "cgck_steer_work_bytes", "cgck_steer", "cgck_rss_steer_desc", "cgck_test_steer_plan",
     "cgck_l2_desc", "cgck_synth_eth", "cgck_test_l2_pass",
     "cgck_l4_desc", "cgck_test_l4_pass",
+    "cgck_l4_build", "cgck_l4_build_hdr_bytes", "cgck_test_l4_build_pass", "cgck_test_l4_build_store",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -244,6 +271,12 @@ def bind(path):
     if hasattr(L, "cgck_l4_desc"):             # the segment parser (an older build loads without it)
         L.cgck_l4_desc.argtypes = [_vp, _vp, _vp, _u64, ctypes.POINTER(L4Res), _vp]
         L.cgck_test_l4_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
+    if hasattr(L, "cgck_l4_build"):            # the frame builder (an older build loads without it)
+        L.cgck_l4_build.argtypes = [_vp, _vp, _u64, ctypes.POINTER(L4BuildIn), ctypes.POINTER(L4BuildRes), _vp]
+        L.cgck_l4_build_hdr_bytes.restype = _u32
+        L.cgck_l4_build_hdr_bytes.argtypes = [ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8]
+        L.cgck_test_l4_build_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
+        L.cgck_test_l4_build_store.argtypes = [ctypes.c_int]
     L.cgck_dst_cache.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32, _vp, _vp]
     L.cgck_dst_cache_host.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32,
                                       ctypes.POINTER(_u32)]
@@ -310,6 +343,21 @@ tcp_cksum = udp_cksum
 def ip_cksum(buf, ip_off=0):
     """ip_cksum(ip) = in_cksum(ip, ip->ip_hl << 2) — subr.h:176."""
     return in_cksum(buf, ip_off, (int(buf[ip_off]) & 0x0F) << 2)
+
+
+L4B_STORE_DEFAULT, L4B_STORE_DIRECT, L4B_STORE_TURNED = 0, 1, 2
+
+
+def l4_build_store(shape):
+    """cgck_test_l4_build_store: pin l4b_kernel's store shape for the process
+    (L4B_STORE_*); returns the previous value."""
+    return _check(load().cgck_test_l4_build_store(shape), "cgck_test_l4_build_store")
+
+
+def l4_build_hdr_bytes(flow_flags, cls, opt):
+    """cgck_l4_build_hdr_bytes: the bytes cgck_l4_build writes in front of the payload
+    for a flow's flags, a class byte and a seg's opt; 0 when it refuses them."""
+    return load().cgck_l4_build_hdr_bytes(flow_flags, cls, opt)
 
 
 def _u8(a):
@@ -756,6 +804,23 @@ class Engine:
         """cgck_test_l4_pass: frames one pass of l4d_kernel's grid covers on this device."""
         f = _u64()
         _check(load().cgck_test_l4_pass(self.ctx, ctypes.byref(f)), "cgck_test_l4_pass")
+        return f.value
+
+    def l4_build(self, base, n, slot, seg, flow, nflow, cls=None, fidx=None, ip_id0=0, ip_off=0, raw_out=None,
+                 desc_out=None, cls_out=None, count=None, stream=None):
+        """cgck_l4_build: Ethernet + IP + TCP / UDP headers of n frames written into the
+        slots `slot` describes, from seg (SEG_DTYPE[n]) and flow (FLOW_DTYPE[nflow])
+        records; device pointers or None (cls: every frame TCP; fidx: frame k uses
+        flow[k]).  Each output is optional (raw_out, desc_out: DESC_DTYPE[n]; cls_out:
+        u8[n]; count: u32[BLD_NCOUNT], accumulated).  Asynchronous."""
+        arg = L4BuildIn(slot, seg, cls, flow, fidx, nflow, ip_id0, ip_off)
+        res = L4BuildRes(raw_out, desc_out, cls_out, count)
+        _check(load().cgck_l4_build(self.ctx, base, n, ctypes.byref(arg), ctypes.byref(res), stream), "cgck_l4_build")
+
+    def l4_build_pass_frames(self):
+        """cgck_test_l4_build_pass: frames one pass of l4b_kernel's grid covers on this device."""
+        f = _u64()
+        _check(load().cgck_test_l4_build_pass(self.ctx, ctypes.byref(f)), "cgck_test_l4_build_pass")
         return f.value
 
     def synth_eth(self, base, desc, raw, n, vlan_every, seed, stream=None):

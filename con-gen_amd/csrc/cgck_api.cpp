@@ -1180,6 +1180,73 @@ extern "C" int cgck_test_l4_pass(cgck_ctx_t *c, uint64_t *frames)
 	return 0;
 }
 
+// Frames from segment records (cgck_l4b.hip): one launch, no scratch.  The store
+// shape is the product's (kL4bTurned) unless cgck_test_l4_build_store pinned one.
+static constexpr bool kL4bTurned = false; // the A/B of DESIGN.md §5.14: turned is no faster
+static std::atomic<int> g_l4b_store{0};
+
+extern "C" int cgck_l4_build(cgck_ctx_t *c, void *base, uint64_t n, const cgck_l4_build_in_t *in,
+			     const cgck_l4_build_res_t *res, void *stream)
+{
+	static const cgck_l4_build_res_t none = {};
+	if (!c || !base || !in)
+		return set_err(-EINVAL, "cgck_l4_build: NULL context, base or in");
+	if (!res)
+		res = &none;
+	if (n && (!in->slot || !in->seg || !in->flow))
+		return set_err(-EINVAL, "cgck_l4_build: NULL slot, seg or flow");
+	if (((uintptr_t)in->slot & 3) != 0 || ((uintptr_t)res->raw_out & 3) != 0 || ((uintptr_t)res->desc_out & 3) != 0)
+		return set_err(-EINVAL, "cgck_l4_build: descriptors must be 4-byte aligned");
+	if (((uintptr_t)in->seg & 15) != 0 || ((uintptr_t)in->flow & 15) != 0)
+		return set_err(-EINVAL, "cgck_l4_build: seg and flow must be 16-byte aligned");
+	if ((res->raw_out && res->raw_out == in->slot) || (res->desc_out && res->desc_out == in->slot) ||
+	    (res->raw_out && res->raw_out == res->desc_out))
+		return set_err(-EINVAL, "cgck_l4_build: raw_out and desc_out must be neither slot nor each other");
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	L4bParams p = {};
+	p.base = (uint8_t *)base;
+	p.slot = in->slot;
+	p.seg = in->seg;
+	p.cls = in->cls;
+	p.flow = in->flow;
+	p.fidx = in->fidx;
+	p.n = n;
+	p.nflow = in->nflow;
+	p.ip_id0 = in->ip_id0;
+	p.ip_off = in->ip_off;
+	p.raw_out = res->raw_out;
+	p.desc_out = res->desc_out;
+	p.cls_out = res->cls;
+	p.count = res->count;
+	const int shape = g_l4b_store.load(std::memory_order_relaxed);
+	HIP_TRY(launch_l4b(p, shape == 0 ? kL4bTurned : shape == 2, c->num_cus, pick(c, stream)));
+	c->last_kernel = t_kernel;
+	return 0;
+}
+
+extern "C" uint32_t cgck_l4_build_hdr_bytes(uint8_t flow_flags, uint8_t cls, uint8_t opt)
+{
+	const uint32_t l = l4b_lengths(flow_flags, cls, opt);
+	return (l & 255u) + ((l >> 8) & 255u) + (l >> 16);
+}
+
+extern "C" int cgck_test_l4_build_store(int shape)
+{
+	if (shape < 0 || shape > 2)
+		return set_err(-EINVAL, "cgck_test_l4_build_store: shape must be 0 (the product's), 1 (direct) or 2 (turned)");
+	return g_l4b_store.exchange(shape, std::memory_order_relaxed);
+}
+
+extern "C" int cgck_test_l4_build_pass(cgck_ctx_t *c, uint64_t *frames)
+{
+	if (!c || !frames)
+		return set_err(-EINVAL, "cgck_test_l4_build_pass: NULL argument");
+	*frames = frame_pass_frames(c->num_cus);
+	return 0;
+}
+
 extern "C" int cgck_dst_cache(cgck_ctx_t *c, const cgck_dst_params_t *prm, cgck_dst_entry_t *out, uint32_t cap,
 			      uint32_t *count, void *stream)
 {

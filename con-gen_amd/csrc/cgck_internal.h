@@ -220,10 +220,42 @@ struct L4dParams {
 	uint32_t *count;
 };
 
-// Frames that the workgroups one launch of rssf_kernel, l2d_kernel or l4d_kernel
-// runs at most cover per pass (cgck_frame.h).
+// Frames from segment records (cgck_l4b.hip; include/cgck.h, section 3).  slot:
+// where the frames go; cls, fidx and each output may be nullptr.
+struct L4bParams {
+	uint8_t *base;
+	const void *slot;
+	const void *seg;
+	const uint8_t *cls;
+	const void *flow;
+	const uint32_t *fidx;
+	uint64_t n;
+	uint32_t nflow;
+	uint32_t ip_id0, ip_off;
+	void *raw_out;
+	void *desc_out;
+	uint8_t *cls_out;
+	uint32_t *count;
+};
+
+// Frames that the workgroups one launch of rssf_kernel, l2d_kernel, l4d_kernel or
+// l4b_kernel runs at most cover per pass (cgck_frame.h).
 uint64_t frame_pass_frames(int num_cus);
 hipError_t launch_l4d(const L4dParams &p, int num_cus, hipStream_t st);
+// turned: the header's whole 16-byte granules leave through LDS (l4b_kernel<.., true>)
+hipError_t launch_l4b(const L4bParams &p, bool turned, int num_cus, hipStream_t st);
+// Rules 1 to 3 and the header lengths of cgck_l4_build from a flow's flags, a class
+// byte and a seg's opt (cgck_l4_build_hdr_bytes): h | iph << 8 | l4h << 16, or 0
+// when the frame is refused.
+constexpr uint32_t l4b_lengths(uint32_t flow_flags, uint32_t cls, uint32_t opt)
+{
+	const uint32_t c = cls & 15u;
+	if (c > 1u || (flow_flags & ~3u) != 0 || (c == 0 && (opt & ~7u) != 0))
+		return 0;
+	const uint32_t h = (flow_flags & 2u) ? 18u : 14u, iph = (flow_flags & 1u) ? 40u : 20u;
+	const uint32_t l4h = c == 1u ? 8u : 20u + 4u * (opt & 1u) + 2u * (opt & 2u) + 3u * (opt & 4u);
+	return h | iph << 8 | l4h << 16;
+}
 hipError_t launch_rssf(const RssfParams &p, int num_cus, hipStream_t st);
 hipError_t launch_steer(const SteerParams &p, hipStream_t st);
 hipError_t launch_toeplitz(const RssParams &p, int num_cus, hipStream_t st);

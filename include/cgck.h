@@ -869,6 +869,126 @@ typedef struct cgck_l4_res {   /* device memory; each optional (NULL); at least 
 int cgck_l4_desc(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *desc, uint64_t n,
 		 const cgck_l4_res_t *res, void *stream);
 
+/* Frames from segment records: the inverse of cgck_l2_desc + cgck_l4_desc, and the
+ * transmit side's first step.  con-gen's product is header-only segments (SYNs,
+ * ACKs, FINs, RSTs, keepalives: tcp_output.c:253-304,359-418, tcp_subr.c:52-123,
+ * ip_output.c:42-68, gbtcp/tcp.c:381-450) whose every byte follows from a tuple and
+ * a handful of numbers.  cgck_l4_build writes Ethernet + IPv4 / IPv6 + TCP / UDP
+ * headers into ring slots from flow records (the tuple and the link header) and
+ * segment records (cgck_seg_t: the numbers), one kernel over the burst, with both
+ * checksums final for a segment without payload.  The tuples may come from
+ * cgck_dst_cache, or be cgck_l4_desc's records edited into replies (tcp_respond's
+ * swap of addresses and ports is the caller's edit: there is no TCP state here).
+ *
+ * Contract, total over every input byte string.  For frame k, F is the bytes at
+ * base + slot[k].frame_off + slot[k].l3_off, cap = slot[k].ip_len the bytes the
+ * slot has from there, s = seg[k].  The class, by these rules in order:
+ *  1. c = cls ? cls[k] & 15 : CGCK_SEG_TCP.  c neither CGCK_SEG_TCP nor
+ *     CGCK_SEG_UDP: SKIP (a caller may pass cgck_l4_desc's own class array and
+ *     build only what it parsed).
+ *  2. f = fidx ? fidx[k] : k.  f >= nflow, or flow[f].flags with a bit outside
+ *     CGCK_FLOW_IP6 | CGCK_FLOW_VLAN: BADFLOW.  Otherwise CGCK_BLD_IP6 is set
+ *     whenever the flow is IPv6, whatever class follows.
+ *  3. BADSEG.  TCP: s.opt & ~(CGCK_SEG_MSS | CGCK_SEG_WS | CGCK_SEG_TS) (which
+ *     includes CGCK_SEG_OPT_BAD), or CGCK_SEG_WS with s.wscale > 14.  UDP:
+ *     s.pay_len > 65527.
+ *  4. h = 14, or 18 with CGCK_FLOW_VLAN; iph = 20, or 40 for IPv6; l4h = 8 for
+ *     UDP, for TCP 20 + 4 [MSS] + 4 [WS] + 12 [TS]; total = iph + l4h + s.pay_len;
+ *     L = h + total.  L > cap, or slot[k].l3_off + h > 65535: NOROOM.
+ *  5. Otherwise the frame is built, class TCP or UDP, with CGCK_BLD_PAYLOAD when
+ *     s.pay_len > 0.
+ * Of s the call consults sport, dport, seq, ack, win, th_flags, opt, mss, wscale,
+ * ts_val, ts_ecr and pay_len; l4_off and hdr_len are ignored, so a record of
+ * cgck_l4_desc can come back edited.
+ * Bytes of a built frame:
+ *   Ethernet.  F[0..6) = eth_dst, F[6..12) = eth_src; with VLAN 81 00 and the TCI
+ *     big-endian; the ethertype 08 00 or 86 DD at F[h-2..h).
+ *   IPv4.  45 00, total big-endian, the id (ip_id0 + k) & 0xFFFF big-endian
+ *     (ip_output.c:40,53), ip_off big-endian, ttl, proto (6 / 17), the header sum,
+ *     laddr[0..4), faddr[0..4).
+ *   IPv6.  60 00 00 00, the payload length l4h + pay_len big-endian, next header =
+ *     proto, hop limit = ttl, laddr, faddr (16 bytes each).  No extension headers.
+ *   TCP.  sport and dport as stored (the two bytes a little-endian store of the
+ *     u16 gives: the inverse of cgck_seg_t's rule), seq and ack big-endian, the
+ *     data offset (l4h / 4) << 4 with a zero low nibble, th_flags, win big-endian,
+ *     the sum, urgent pointer 0; then, each whenever its bit is set, in
+ *     tcp_output.c:255-302's layout and order, 02 04 mss, 01 03 03 wscale, and
+ *     01 01 08 0A ts_val ts_ecr.  The builder writes what it is told: MSS on a
+ *     segment without SYN is the caller's business.
+ *   UDP.  The ports, ulen = 8 + pay_len big-endian, the sum.
+ *   Sums follow this header's `out` rule.  The IPv4 header sum is always final.
+ *     With pay_len == 0 the L4 sum is final, over the 12-byte pseudo-header for
+ *     IPv4 and the 40-byte one for IPv6, as under CGCK_L4 / CGCK_IP6.  With
+ *     pay_len > 0 the L4 field is written as zero and CGCK_BLD_PAYLOAD says so;
+ *     desc_out is then the descriptor array for cgck_desc(CGCK_L4 |
+ *     CGCK_ZERO_FIELDS | CGCK_STORE [| CGCK_IP6]).  The builder never reads or
+ *     sums payload: a streamed fill does that at its own rate.
+ * What is written: exactly the bytes F[0, h + iph + l4h) of a built frame.
+ * Payload already in the slot behind them and every byte before F stay untouched;
+ * nothing of a slot whose frame is not built is written.  The kernel never reads
+ * a slot's bytes and does no read-modify-write at a wider granularity, so frames
+ * packed back to back may share dwords and 16-byte granules.  The slots of one
+ * call must not overlap; the order between frames is unspecified, as for
+ * CGCK_STORE.
+ * Outputs.  raw_out[k] = {frame_off, slot.l3_off, L}: what a transport sends and
+ * what cgck_l2_desc takes.  desc_out[k] = {frame_off, slot.l3_off + h, total}: what
+ * cgck_desc and cgck_l4_desc take.  A frame that is not built gets {frame_off,
+ * slot.l3_off, 0} in both (ip_len == 0 is the library's "no frame").  cls[k] =
+ * class | flags.  count[class] += 1 per frame, count[6] += 1 per built IPv6 frame,
+ * count[7] += 1 per built frame with CGCK_BLD_PAYLOAD.
+ *
+ * Execution.  Asynchronous on `stream` (NULL: the context's).  n == 0 returns 0,
+ * launches nothing and writes nothing.  The inputs are never written.  The library
+ * keeps no scratch for this call.  One kernel, l4b_kernel; DESIGN.md §5.14 has its
+ * measurements.
+ * -EINVAL: a NULL ctx, base or in; with n > 0 a NULL slot, seg or flow; a slot,
+ * raw_out or desc_out that is not 4-byte aligned, a seg or flow that is not
+ * 16-byte aligned; raw_out or desc_out equal to slot or to each other.  Every
+ * 16-bit value is a legal ip_off, so none is refused.
+ * Out of scope: payload sums in the builder; ICMP, IP options and
+ * IPv6 extension headers; a host form (a host burst's headers are cheaper to
+ * write on the host, as for cgck_l2_desc and cgck_l4_desc); any TCP state. */
+typedef struct cgck_flow {       /* 48 bytes; arrays 16-byte aligned */
+	uint8_t  eth_dst[6], eth_src[6];
+	uint16_t vlan_tci;           /* host order; written with CGCK_FLOW_VLAN */
+	uint8_t  flags;              /* CGCK_FLOW_IP6 | CGCK_FLOW_VLAN */
+	uint8_t  ttl;                /* ip_ttl / hop limit */
+	uint8_t  laddr[16];          /* source address as on the wire; IPv4: bytes 0..3, the rest ignored */
+	uint8_t  faddr[16];          /* destination address, likewise */
+} cgck_flow_t;
+enum { CGCK_FLOW_IP6 = 1, CGCK_FLOW_VLAN = 2 };
+
+typedef struct cgck_l4_build_in {   /* pointers are device memory */
+	const cgck_desc_t *slot;  /* [n] where frame k goes: frame_off; l3_off = the Ethernet header's offset
+	                             in the slot; ip_len = cap, the bytes the slot has from there */
+	const cgck_seg_t  *seg;   /* [n], 16-byte aligned */
+	const uint8_t     *cls;   /* [n] or NULL (every frame TCP): low nibble CGCK_SEG_TCP / CGCK_SEG_UDP */
+	const cgck_flow_t *flow;  /* [nflow], 16-byte aligned */
+	const uint32_t    *fidx;  /* [n] or NULL (frame k uses flow[k]) */
+	uint32_t nflow;
+	uint16_t ip_id0;          /* IPv4 frame k carries id (ip_id0 + k) & 0xFFFF (ip_output.c:40,53) */
+	uint16_t ip_off;          /* host order: 0x4000 as bsd44's ip_output, 0 as gbtcp's tcp_fill */
+} cgck_l4_build_in_t;
+
+typedef struct cgck_l4_build_res {  /* device memory; each optional; res itself may be NULL */
+	cgck_desc_t *raw_out;   /* [n] {frame_off, slot.l3_off, L}: what a transport sends, what cgck_l2_desc takes */
+	cgck_desc_t *desc_out;  /* [n] {frame_off, slot.l3_off + h, total}: what cgck_desc / cgck_l4_desc take */
+	uint8_t     *cls;       /* [n] class | flags */
+	uint32_t    *count;     /* u32[CGCK_BLD_NCOUNT] running counters (+=) */
+} cgck_l4_build_res_t;
+
+enum { CGCK_BLD_TCP = 0, CGCK_BLD_UDP = 1, CGCK_BLD_SKIP = 2, CGCK_BLD_BADFLOW = 3,
+       CGCK_BLD_BADSEG = 4, CGCK_BLD_NOROOM = 5, CGCK_BLD_NCLASS = 6 };   /* low nibble */
+enum { CGCK_BLD_IP6 = 1u << 4, CGCK_BLD_PAYLOAD = 1u << 5 };              /* flag bits  */
+#define CGCK_BLD_NCOUNT 8  /* [class] for the six classes, [6] built IPv6 frames, [7] built frames with PAYLOAD */
+
+int cgck_l4_build(cgck_ctx_t *ctx, void *base, uint64_t n, const cgck_l4_build_in_t *in,
+		  const cgck_l4_build_res_t *res, void *stream);
+/* Bytes in front of the payload (h + IP header + transport header) for a flow's flags, a class byte and
+ * a seg's opt; 0 when rule 1 or 3 above would refuse it (or rule 2 the flags).  Pure: no device, no
+ * context. */
+uint32_t cgck_l4_build_hdr_bytes(uint8_t flow_flags, uint8_t cls, uint8_t opt);
+
 /* One dst-cache entry: the fields thread_init_dst_cache fills in struct
  * ip_socket (con-gen.c:344-349; subr.h:218-228).  16 bytes. */
 typedef struct cgck_dst_entry {
@@ -969,6 +1089,13 @@ int cgck_test_steer_plan(uint64_t n, uint32_t queue_num, uint32_t *tile, uint32_
 int cgck_test_l2_pass(cgck_ctx_t *ctx, uint64_t *frames);
 /* The same for cgck_l4_desc's grid. */
 int cgck_test_l4_pass(cgck_ctx_t *ctx, uint64_t *frames);
+/* The same for cgck_l4_build's grid. */
+int cgck_test_l4_build_pass(cgck_ctx_t *ctx, uint64_t *frames);
+/* Pin the store shape of l4b_kernel for every later cgck_l4_build of the process (the tests of both
+ * shapes and the A/B of tools/l4b_ab.py): 0 the product's choice, 1 every dword from
+ * its own lane (l4b_kernel<.., false>), 2 whole 16-byte granules turned through LDS (<.., true>).
+ * Returns the previous value; -EINVAL for any other. */
+int cgck_test_l4_build_store(int shape);
 
 #ifdef __cplusplus
 }
