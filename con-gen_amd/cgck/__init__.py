@@ -140,6 +140,31 @@ class L4BuildRes(ctypes.Structure):
                 ("count", ctypes.c_void_p)]
 
 
+# cgck_pcb_build / cgck_pcb_lookup: the connection record, the kind of a frame's
+# lookup, the running counters and the ports a listening socket binds.
+CONN_DTYPE = np.dtype([("flow", "<u4"), ("lport", "<u2"), ("fport", "<u2"), ("proto", "u1"), ("rsv", "u1", (3,))])
+assert CONN_DTYPE.itemsize == 12
+PCB_HIT, PCB_BOUND, PCB_MISS, PCB_SKIP, PCB_NONE = 0, 1, 2, 3, 4
+PCB_NCLASS = 5
+PCB_NCOUNT = 6          # [kind] for the five kinds, [5] HITs on IPv6 frames
+PCB_NBOUND = 5000       # EPHEMERAL_MIN
+PCB_MODE_CHAIN = 1      # cgck_test_pcb_mode: every key's home slot is the table's last
+PCB_MODE_UNTAGGED = 2   # cgck_test_pcb_mode: 4-byte slots, the index alone
+
+
+class Pcb(ctypes.Structure):
+    """cgck_pcb_t: the caller's connection and flow arrays, the table and the bound ports."""
+    _fields_ = [("conn", ctypes.c_void_p), ("nconn", ctypes.c_uint32), ("flow", ctypes.c_void_p),
+                ("nflow", ctypes.c_uint32), ("table", ctypes.c_void_p), ("table_bytes", ctypes.c_size_t),
+                ("bound", ctypes.c_void_p)]
+
+
+class PcbRes(ctypes.Structure):
+    """cgck_pcb_res_t: the optional outputs of the connection lookup."""
+    _fields_ = [("idx", ctypes.c_void_p), ("fidx", ctypes.c_void_p), ("kind", ctypes.c_void_p),
+                ("count", ctypes.c_void_p)]
+
+
 class SteerRes(ctypes.Structure):
     """cgck_steer_res_t: the optional outputs of the partition by queue id."""
     _fields_ = [("qoff", ctypes.c_void_p), ("perm", ctypes.c_void_p), ("slot", ctypes.c_void_p),
@@ -169,6 +194,7 @@ EXPORTS = (
     "cgck_l2_desc", "cgck_synth_eth", "cgck_test_l2_pass",
     "cgck_l4_desc", "cgck_test_l4_pass",
     "cgck_l4_build", "cgck_l4_build_hdr_bytes", "cgck_test_l4_build_pass", "cgck_test_l4_build_store",
+    "cgck_pcb_table_bytes", "cgck_pcb_build", "cgck_pcb_lookup", "cgck_test_pcb_pass", "cgck_test_pcb_mode",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -277,6 +303,13 @@ def bind(path):
         L.cgck_l4_build_hdr_bytes.argtypes = [ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8]
         L.cgck_test_l4_build_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
         L.cgck_test_l4_build_store.argtypes = [ctypes.c_int]
+    if hasattr(L, "cgck_pcb_lookup"):          # the connection lookup (an older build loads without it)
+        L.cgck_pcb_table_bytes.restype = ctypes.c_size_t
+        L.cgck_pcb_table_bytes.argtypes = [_u32]
+        L.cgck_pcb_build.argtypes = [_vp, ctypes.POINTER(Pcb), _vp, _vp]
+        L.cgck_pcb_lookup.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, ctypes.POINTER(Pcb), ctypes.POINTER(PcbRes), _vp]
+        L.cgck_test_pcb_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
+        L.cgck_test_pcb_mode.argtypes = [ctypes.c_int]
     L.cgck_dst_cache.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32, _vp, _vp]
     L.cgck_dst_cache_host.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32,
                                       ctypes.POINTER(_u32)]
@@ -358,6 +391,19 @@ def l4_build_hdr_bytes(flow_flags, cls, opt):
     """cgck_l4_build_hdr_bytes: the bytes cgck_l4_build writes in front of the payload
     for a flow's flags, a class byte and a seg's opt; 0 when it refuses them."""
     return load().cgck_l4_build_hdr_bytes(flow_flags, cls, opt)
+
+
+def pcb_table_bytes(nconn):
+    """cgck_pcb_table_bytes: the bytes cgck_pcb_build's table needs for nconn entries
+    (0 for nconn above 1 << 30)."""
+    return load().cgck_pcb_table_bytes(nconn)
+
+
+def pcb_mode(mode):
+    """cgck_test_pcb_mode: pin the home slot (PCB_MODE_CHAIN) and the table shape
+    (PCB_MODE_UNTAGGED) of every later pcb_build and pcb_lookup of the process;
+    returns the previous value."""
+    return _check(load().cgck_test_pcb_mode(mode), "cgck_test_pcb_mode")
 
 
 def _u8(a):
@@ -821,6 +867,26 @@ class Engine:
         """cgck_test_l4_build_pass: frames one pass of l4b_kernel's grid covers on this device."""
         f = _u64()
         _check(load().cgck_test_l4_build_pass(self.ctx, ctypes.byref(f)), "cgck_test_l4_build_pass")
+        return f.value
+
+    def pcb_build(self, pcb, stat=None, stream=None):
+        """cgck_pcb_build: the device hash table of pcb (a Pcb) from its connection
+        records; stat: u32[4], written.  Asynchronous."""
+        _check(load().cgck_pcb_build(self.ctx, ctypes.byref(pcb), stat, stream), "cgck_pcb_build")
+
+    def pcb_lookup(self, base, desc, seg, n, pcb, cls=None, idx=None, fidx=None, kind=None, count=None, stream=None):
+        """cgck_pcb_lookup: the connection of each of the n frames desc and seg
+        (cgck_l4_desc's records) describe, against pcb's table; each output is optional
+        (idx, fidx: u32[n]; kind: u8[n]; count: u32[PCB_NCOUNT], accumulated).
+        Asynchronous."""
+        res = PcbRes(idx, fidx, kind, count)
+        _check(load().cgck_pcb_lookup(self.ctx, base, desc, seg, cls, n, ctypes.byref(pcb), ctypes.byref(res), stream),
+               "cgck_pcb_lookup")
+
+    def pcb_pass_frames(self):
+        """cgck_test_pcb_pass: frames one pass of pcbl_kernel's grid covers on this device."""
+        f = _u64(0)
+        _check(load().cgck_test_pcb_pass(self.ctx, ctypes.byref(f)), "cgck_test_pcb_pass")
         return f.value
 
     def synth_eth(self, base, desc, raw, n, vlan_every, seed, stream=None):

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "cgck_host.h"
+#include "cgck_pcb_probe.h"
 #include "cgck_steer_plan.h"
 
 using namespace cgck;
@@ -1245,6 +1246,118 @@ extern "C" int cgck_test_l4_build_pass(cgck_ctx_t *c, uint64_t *frames)
 		return set_err(-EINVAL, "cgck_test_l4_build_pass: NULL argument");
 	*frames = frame_pass_frames(c->num_cus);
 	return 0;
+}
+
+// Per-frame connection lookup (cgck_pcb.hip): a memset and one launch for the build,
+// one launch for the lookup, no scratch.  The table shape is the product's
+// (kPcbTagged) unless cgck_test_pcb_mode's bit 1 asks for the other.
+static constexpr bool kPcbTagged = true; // the A/B of DESIGN.md §5.15
+static std::atomic<int> g_pcb_mode{0};
+
+// The checks the two calls share; nullptr when pcb passes.
+static const char *pcb_refused(const cgck_pcb_t *pcb)
+{
+	if (((uintptr_t)pcb->conn & 3) != 0 || ((uintptr_t)pcb->bound & 3) != 0)
+		return "conn and bound must be 4-byte aligned";
+	if (((uintptr_t)pcb->flow & 15) != 0 || ((uintptr_t)pcb->table & 15) != 0)
+		return "flow and table must be 16-byte aligned";
+	if (pcb->nconn > kPcbMaxConn)
+		return "nconn above 1 << 30";
+	if (pcb->nconn && !pcb->conn)
+		return "NULL conn";
+	if (pcb->nflow && !pcb->flow)
+		return "NULL flow";
+	if (!pcb->table)
+		return "NULL table";
+	if (pcb->table_bytes < cgck_pcb_table_bytes(pcb->nconn))
+		return "table_bytes below cgck_pcb_table_bytes(nconn)";
+	return nullptr;
+}
+
+static PcbTable pcb_table(const cgck_pcb_t *pcb, int mode)
+{
+	PcbTable t = {};
+	t.conn = pcb->conn;
+	t.flow = pcb->flow;
+	t.table = pcb->table;
+	t.nconn = pcb->nconn;
+	t.nflow = pcb->nflow;
+	t.mask = pcb_slots(pcb->nconn) - 1;
+	t.chain = mode & 1;
+	return t;
+}
+
+extern "C" int cgck_pcb_build(cgck_ctx_t *c, const cgck_pcb_t *pcb, uint32_t *stat, void *stream)
+{
+	if (!c || !pcb)
+		return set_err(-EINVAL, "cgck_pcb_build: NULL context or pcb");
+	if (const char *why = pcb_refused(pcb))
+		return set_err(-EINVAL, "cgck_pcb_build: %s", why);
+	if (((uintptr_t)stat & 3) != 0)
+		return set_err(-EINVAL, "cgck_pcb_build: stat must be 4-byte aligned");
+	HIP_TRY(hipSetDevice(c->device));
+	const int mode = g_pcb_mode.load(std::memory_order_relaxed);
+	PcbbParams p = {};
+	p.t = pcb_table(pcb, mode);
+	p.stat = stat;
+	HIP_TRY(launch_pcbb(p, (mode & 2) ? false : kPcbTagged, pick(c, stream)));
+	if (pcb->nconn)
+		c->last_kernel = t_kernel;
+	return 0;
+}
+
+extern "C" int cgck_pcb_lookup(cgck_ctx_t *c, const void *base, const cgck_desc_t *desc, const cgck_seg_t *seg,
+			       const uint8_t *cls, uint64_t n, const cgck_pcb_t *pcb, const cgck_pcb_res_t *res,
+			       void *stream)
+{
+	if (!c || !pcb || !res || !base)
+		return set_err(-EINVAL, "cgck_pcb_lookup: NULL context, pcb, res or base");
+	if (n && (!desc || !seg))
+		return set_err(-EINVAL, "cgck_pcb_lookup: NULL descriptors or seg");
+	if (!res->idx && !res->fidx && !res->kind && !res->count)
+		return set_err(-EINVAL, "cgck_pcb_lookup: every output is NULL");
+	if (((uintptr_t)desc & 3) != 0 || ((uintptr_t)res->idx & 3) != 0 || ((uintptr_t)res->fidx & 3) != 0 ||
+	    ((uintptr_t)res->count & 3) != 0)
+		return set_err(-EINVAL, "cgck_pcb_lookup: desc, idx, fidx and count must be 4-byte aligned");
+	if (((uintptr_t)seg & 15) != 0)
+		return set_err(-EINVAL, "cgck_pcb_lookup: seg must be 16-byte aligned");
+	if (const char *why = pcb_refused(pcb))
+		return set_err(-EINVAL, "cgck_pcb_lookup: %s", why);
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	const int mode = g_pcb_mode.load(std::memory_order_relaxed);
+	PcblParams p = {};
+	p.base = (const uint8_t *)base;
+	p.desc = desc;
+	p.seg = seg;
+	p.cls = cls;
+	p.n = n;
+	p.zero = c->d_zero;
+	p.t = pcb_table(pcb, mode);
+	p.bound = pcb->bound;
+	p.idx = res->idx;
+	p.fidx = res->fidx;
+	p.kind = res->kind;
+	p.count = res->count;
+	HIP_TRY(launch_pcbl(p, (mode & 2) ? false : kPcbTagged, c->num_cus, pick(c, stream)));
+	c->last_kernel = t_kernel;
+	return 0;
+}
+
+extern "C" int cgck_test_pcb_pass(cgck_ctx_t *c, uint64_t *frames)
+{
+	if (!c || !frames)
+		return set_err(-EINVAL, "cgck_test_pcb_pass: NULL argument");
+	*frames = frame_pass_frames(c->num_cus);
+	return 0;
+}
+
+extern "C" int cgck_test_pcb_mode(int mode)
+{
+	if (mode < 0 || mode > 3)
+		return set_err(-EINVAL, "cgck_test_pcb_mode: mode must be within 0..3");
+	return g_pcb_mode.exchange(mode, std::memory_order_relaxed);
 }
 
 extern "C" int cgck_dst_cache(cgck_ctx_t *c, const cgck_dst_params_t *prm, cgck_dst_entry_t *out, uint32_t cap,

@@ -238,8 +238,45 @@ struct L4bParams {
 	uint32_t *count;
 };
 
-// Frames that the workgroups one launch of rssf_kernel, l2d_kernel, l4d_kernel or
-// l4b_kernel runs at most cover per pass (cgck_frame.h).
+// Per-frame connection lookup (cgck_pcb.hip; include/cgck.h, section 3).  PcbTable
+// is what the build and the lookup share: the caller's arrays, the table, mask =
+// pcb_slots(nconn) - 1 (cgck_pcb_probe.h) and chain, cgck_test_pcb_mode's bit 0.
+struct PcbTable {
+	const void *conn;
+	const void *flow;
+	void *table;
+	uint32_t nconn, nflow;
+	uint32_t mask, chain;
+};
+
+struct PcbbParams {
+	PcbTable t;
+	uint32_t *stat; // zeroed by the launcher; may be nullptr
+};
+
+// desc, seg: the burst; cls and bound may be nullptr, and each output.
+struct PcblParams {
+	const uint8_t *base;
+	const void *desc;
+	const void *seg;
+	const uint8_t *cls;
+	uint64_t n;
+	const void *zero;
+	PcbTable t;
+	const uint32_t *bound;
+	uint32_t *idx;
+	uint32_t *fidx;
+	uint8_t *kind;
+	uint32_t *count;
+};
+
+// tagged: 8-byte slots {idx, tag} (pcbb_kernel<true>, pcbl_kernel<.., true>), else
+// 4-byte slots of the index alone.  launch_pcbb initialises the table and stat.
+hipError_t launch_pcbb(const PcbbParams &p, bool tagged, hipStream_t st);
+hipError_t launch_pcbl(const PcblParams &p, bool tagged, int num_cus, hipStream_t st);
+
+// Frames that the workgroups one launch of rssf_kernel, l2d_kernel, l4d_kernel,
+// l4b_kernel or pcbl_kernel runs at most cover per pass (cgck_frame.h).
 uint64_t frame_pass_frames(int num_cus);
 hipError_t launch_l4d(const L4dParams &p, int num_cus, hipStream_t st);
 // turned: the header's whole 16-byte granules leave through LDS (l4b_kernel<.., true>)

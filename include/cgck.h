@@ -989,6 +989,112 @@ int cgck_l4_build(cgck_ctx_t *ctx, void *base, uint64_t n, const cgck_l4_build_i
  * context. */
 uint32_t cgck_l4_build_hdr_bytes(uint8_t flow_flags, uint8_t cls, uint8_t opt);
 
+/* Per-frame connection lookup: the first thing both stacks do with a parsed
+ * segment, in_pcblookup (bsd44/in_pcb.c:167-192, called from tcp_input.c:118 and
+ * udp_usrreq.c:97; ip_socket_get, subr.c:580-596), over a tuple table the caller
+ * owns.  cgck_l4_desc's records go in, and the index cgck_l4_build takes as fidx
+ * comes out, with no host pass between the receive side and the transmit side.
+ * The tuple set of a con-gen worker is fixed for the worker's life (the dst cache,
+ * con-gen.c:291-360), so cgck_pcb_build makes a device hash table once per
+ * dst-cache build and cgck_pcb_lookup resolves every burst against it.  This is a
+ * lookup and holds no TCP state: which socket is open at an index, and what to
+ * answer, stay the caller's.
+ *
+ * Keys.  The key of connection j is (family, proto, laddr, faddr, lport, fport)
+ * with f = flow[conn[j].flow]: the family is f.flags & CGCK_FLOW_IP6; IPv4 uses
+ * bytes 0..3 of f.laddr and f.faddr and ignores the rest, IPv6 all 16; f's MACs,
+ * TCI, TTL and CGCK_FLOW_VLAN bit are not part of the key.  Connection j is valid
+ * when proto != 0, flow < nflow and f.flags has no bit outside IP6 | VLAN.
+ * The key of frame k uses b, the ip_len bytes at base + frame_off + l3_off, and
+ * v = b[0] >> 4, as in_pcblookup(proto, ip_dst, dport, ip_src, sport): family
+ * v == 6; proto 6 or 17 from cls[k] & 15; laddr = ip_dst (v4 b[16..20), v6
+ * b[24..40)); faddr = ip_src (v4 b[12..16), v6 b[8..24)); lport = seg[k].dport,
+ * fport = seg[k].sport.
+ *
+ * Lookup rules, in order, total over every input byte string:
+ *  1. c = cls ? cls[k] & 15 : CGCK_SEG_TCP.  c neither CGCK_SEG_TCP nor
+ *     CGCK_SEG_UDP: SKIP (cgck_l4_desc's own class array may come in, as in
+ *     cgck_l4_build).
+ *  2. NONE when ip_len == 0, when v == 4 with ip_len < 20, when v == 6 with
+ *     ip_len < 40, and for any other v.  The header's own length fields and cls's
+ *     IP6 flag are not consulted; ip_len bounds every read.
+ *  3. The lowest valid j whose key equals the frame's: HIT, idx = j, fidx =
+ *     conn[j].flow.
+ *  4. BOUND with idx = bound[p] when bound != NULL, p = bswap16(seg[k].dport) <
+ *     CGCK_PCB_NBOUND and bound[p] != 0xFFFFFFFF.  Proto and family are not
+ *     compared, as in_pcb.c:186-188 (the reference has no IPv6; the same rule
+ *     applies to it here).
+ *  5. MISS.
+ * Every kind but HIT and BOUND writes idx = 0xFFFFFFFF; every kind but HIT writes
+ * fidx = 0xFFFFFFFF (for cgck_l4_build: BADFLOW, nothing built).  count[kind] += 1
+ * per frame and count[5] += 1 per HIT with v == 6.
+ *
+ * Build.  cgck_pcb_build initialises the table itself (the caller need not zero
+ * it) and inserts every valid connection.  stat, when given, is written, not
+ * accumulated: [0] distinct keys, [1] valid entries whose key equals a lower-index
+ * valid entry's, [2] entries with proto == 0, [3] entries with proto != 0 and a
+ * bad flow (flow >= nflow or a refused flag bit).  The four sum to nconn and each
+ * is determined whatever the order of execution.  The table's layout is private.
+ * It is valid while conn, flow and table stay unchanged.  nconn == 0 is legal:
+ * every frame is then MISS, BOUND, SKIP or NONE.
+ * cgck_pcb_table_bytes(nconn) = 8 * S, S the power of two at or above 2 * nconn
+ * and at least 2; 0 for nconn > 1 << 30.  Pure: no device, no context.
+ *
+ * Execution.  Both calls are asynchronous on `stream` (NULL: the context's).
+ * A lookup with n == 0 launches nothing and writes nothing.  The inputs are never
+ * written.  The library keeps no scratch.  Kernels: pcbb_kernel (a lane per
+ * connection; no lane or workgroup ever waits for another) and pcbl_kernel (a lane
+ * per frame); DESIGN.md §5.15 has the design and the measurements.
+ * -EINVAL: a NULL ctx, pcb, res or base; with n > 0 a NULL desc or seg; every
+ * output NULL; a desc, conn, bound, idx, fidx, count or stat that is not 4-byte
+ * aligned, a seg, flow or table that is not 16-byte aligned; nconn > 1 << 30;
+ * nconn > 0 with a NULL conn; nflow > 0 with a NULL flow; a NULL table;
+ * table_bytes below cgck_pcb_table_bytes(nconn).  The argument checks come before
+ * any device work.
+ *
+ * Safety, part of the contract.  A table that cgck_pcb_build did not produce for
+ * these arrays can cost hits but can never fault: every index read from the table
+ * is compared with nconn, and every conn[j].flow with nflow, before it is used,
+ * and a probe ends after at most the table's slot count.  A reported HIT is always
+ * a true key match, because the compare reads conn and flow.
+ * Out of scope: the socket layer and which socket is open at an
+ * index; incremental insert and delete; in_pcbnotify's quoted-header lookup; a
+ * host form. */
+typedef struct cgck_conn {      /* 12 bytes, arrays 4-byte aligned */
+	uint32_t flow;              /* index into flow[]: the addresses and the family */
+	uint16_t lport, fport;      /* as stored (be16_t), cgck_seg_t's rule */
+	uint8_t  proto;             /* 6, 17, ...; 0: unused entry */
+	uint8_t  rsv[3];            /* ignored */
+} cgck_conn_t;
+
+#define CGCK_PCB_NBOUND 5000    /* EPHEMERAL_MIN (subr.h:62): the ports a listening socket binds */
+
+typedef struct cgck_pcb {       /* pointers are device memory */
+	const cgck_conn_t *conn;    /* [nconn] */
+	uint32_t nconn;             /* <= 1 << 30 */
+	const cgck_flow_t *flow;    /* [nflow], 16-byte aligned: cgck_l4_build's table */
+	uint32_t nflow;
+	void *table;                /* caller-owned, 16-byte aligned */
+	size_t table_bytes;         /* >= cgck_pcb_table_bytes(nconn) */
+	const uint32_t *bound;      /* NULL, or u32[CGCK_PCB_NBOUND]: the index of the socket bound to port p, or 0xFFFFFFFF */
+} cgck_pcb_t;
+
+size_t cgck_pcb_table_bytes(uint32_t nconn);
+int cgck_pcb_build(cgck_ctx_t *ctx, const cgck_pcb_t *pcb, uint32_t *stat /* device u32[4] or NULL */, void *stream);
+
+typedef struct cgck_pcb_res {   /* device memory; each optional; at least one non-NULL */
+	uint32_t *idx;              /* [n] connection index, 0xFFFFFFFF when there is none */
+	uint32_t *fidx;             /* [n] conn[idx].flow for a HIT, else 0xFFFFFFFF */
+	uint8_t  *kind;             /* [n] */
+	uint32_t *count;            /* u32[CGCK_PCB_NCOUNT] running counters (+=) */
+} cgck_pcb_res_t;
+enum { CGCK_PCB_HIT = 0, CGCK_PCB_BOUND = 1, CGCK_PCB_MISS = 2, CGCK_PCB_SKIP = 3, CGCK_PCB_NONE = 4, CGCK_PCB_NCLASS = 5 };
+#define CGCK_PCB_NCOUNT 6       /* [kind] for the five kinds, [5] HITs on IPv6 frames */
+
+int cgck_pcb_lookup(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *desc, const cgck_seg_t *seg,
+		    const uint8_t *cls /* or NULL: every frame TCP */, uint64_t n,
+		    const cgck_pcb_t *pcb, const cgck_pcb_res_t *res, void *stream);
+
 /* One dst-cache entry: the fields thread_init_dst_cache fills in struct
  * ip_socket (con-gen.c:344-349; subr.h:218-228).  16 bytes. */
 typedef struct cgck_dst_entry {
@@ -1096,6 +1202,14 @@ int cgck_test_l4_build_pass(cgck_ctx_t *ctx, uint64_t *frames);
  * its own lane (l4b_kernel<.., false>), 2 whole 16-byte granules turned through LDS (<.., true>).
  * Returns the previous value; -EINVAL for any other. */
 int cgck_test_l4_build_store(int shape);
+/* The same as cgck_test_l4_pass for cgck_pcb_lookup's grid. */
+int cgck_test_pcb_pass(cgck_ctx_t *ctx, uint64_t *frames);
+/* Pin how every later cgck_pcb_build and cgck_pcb_lookup of the process work (the tests and the A/B of
+ * tools/pcb_ab.py); a table is looked up under the mode it was built under.  Bit 0:
+ * every key's home slot is the table's last slot, which forces the longest chain and the wrap-around.
+ * Bit 1: the A/B's other table shape, 4-byte slots that hold the index alone (pcbb_kernel<false>,
+ * pcbl_kernel<.., false>).  Returns the previous value; -EINVAL outside 0..3. */
+int cgck_test_pcb_mode(int mode);
 
 #ifdef __cplusplus
 }
