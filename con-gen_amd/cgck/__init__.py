@@ -195,6 +195,7 @@ EXPORTS = (
     "cgck_l4_desc", "cgck_test_l4_pass",
     "cgck_l4_build", "cgck_l4_build_hdr_bytes", "cgck_test_l4_build_pass", "cgck_test_l4_build_store",
     "cgck_pcb_table_bytes", "cgck_pcb_build", "cgck_pcb_lookup", "cgck_test_pcb_pass", "cgck_test_pcb_mode",
+    "cgck_test_rss_pass",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -310,6 +311,8 @@ def bind(path):
         L.cgck_pcb_lookup.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, ctypes.POINTER(Pcb), ctypes.POINTER(PcbRes), _vp]
         L.cgck_test_pcb_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
         L.cgck_test_pcb_mode.argtypes = [ctypes.c_int]
+    if hasattr(L, "cgck_test_rss_pass"):       # cgck_toeplitz's geometry (an older build loads without it)
+        L.cgck_test_rss_pass.argtypes = [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]
     L.cgck_dst_cache.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32, _vp, _vp]
     L.cgck_dst_cache_host.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32,
                                       ctypes.POINTER(_u32)]
@@ -778,6 +781,13 @@ class Engine:
         _check(load().cgck_toeplitz(self.ctx, data, n, stride, cnt, k.ctypes.data,
                                     len(k) if key_size is None else key_size, mask, out, stream),
                "cgck_toeplitz")
+
+    def rss_pass(self):
+        """cgck_test_rss_pass: (records one pass of toeplitz_kernel's grid covers on this
+        device, 4-record groups the dense kernel's register ring holds before it wraps)."""
+        r, g = _u64(0), _u64(0)
+        _check(load().cgck_test_rss_pass(self.ctx, ctypes.byref(r), ctypes.byref(g)), "cgck_test_rss_pass")
+        return r.value, g.value
 
     @staticmethod
     def rss_spec(key, mask=0xFFFFFFFF, hf=RSS_TCP | RSS_UDP, queue_num=0, key_size=None):

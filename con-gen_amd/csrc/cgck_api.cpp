@@ -874,6 +874,16 @@ extern "C" int cgck_toeplitz(cgck_ctx_t *c, const void *data, uint64_t n, uint64
 	return rss_note_use(c, st);
 }
 
+// launch_toeplitz's geometry on c's device, from the constants it launches with.
+extern "C" int cgck_test_rss_pass(cgck_ctx_t *c, uint64_t *records, uint64_t *groups)
+{
+	if (!c || !records || !groups)
+		return set_err(-EINVAL, "cgck_test_rss_pass: NULL argument");
+	*records = (uint64_t)c->num_cus * kRssPassBlocksPerCu * 256;
+	*groups = (uint64_t)c->num_cus * kRssX4BlocksPerCu * 256 * kRssX4Depth;
+	return 0;
+}
+
 // Per-frame hash of a receive burst (cgck_rssf.hip).  The argument rules the
 // three entry points share; `what` names the caller in the message.
 static int rss_frames_check(const char *what, const cgck_ctx *c, const void *base, const cgck_desc_t *desc,

@@ -122,6 +122,10 @@ constexpr int kDefaultRssVariant = 2;
 // Toeplitz RSS hash (cgck_rss.hip; subr.c:482-530).  `tab` = cnt x 256 u32
 // byte tables derived from the key on the host (rss_tables in cgck_api.cpp).
 constexpr uint32_t kRssLdsMaxCnt = 36; // tables up to 36 KiB are staged in LDS
+// launch_toeplitz's geometry (cgck_test_rss_pass reports it from the same names):
+constexpr int kRssPassBlocksPerCu = 8; // toeplitz_kernel: at most this many 256-record blocks per CU, then it strides
+constexpr int kRssX4BlocksPerCu = 1;   // toeplitz12x4_ab_kernel: blocks per CU
+constexpr int kRssX4Depth = 12;        // and 4-record groups per lane in its register ring
 
 struct RssParams {
 	const uint8_t *data;

@@ -283,7 +283,7 @@ hipError_t launch_toeplitz(const RssParams &p0, int num_cus, hipStream_t st)
 		// (tools/rss_sweep.sh)
 		static const int bpc = [] {
 			const char *e = CGCK_ENV("CGCK_RSS_BPC");
-			return e && atoi(e) > 0 ? atoi(e) : 1;
+			return e && atoi(e) > 0 ? atoi(e) : kRssX4BlocksPerCu;
 		}();
 		// ring depth 12 at 1 block per CU (181 VGPRs, no spills), in-process
 		// A/B chain (tools/ab_inproc.py, profiles/r01/ab_rss_depth_chain.log):
@@ -293,7 +293,7 @@ hipError_t launch_toeplitz(const RssParams &p0, int num_cus, hipStream_t st)
 		static const int depth = [] { // $CGCK_RSS_DEPTH: groups per lane in flight, 2..6, 8, 10, 12, 16
 			const char *e = CGCK_ENV("CGCK_RSS_DEPTH");
 			const int d = e ? atoi(e) : 0;
-			return (d >= 2 && d <= 6) || d == 8 || d == 10 || d == 12 || d == 16 ? d : 12;
+			return (d >= 2 && d <= 6) || d == 8 || d == 10 || d == 12 || d == 16 ? d : kRssX4Depth;
 		}();
 		const uint64_t capb = (uint64_t)num_cus * bpc;
 		const dim3 gb((unsigned)(want < capb ? want : capb));
@@ -348,7 +348,7 @@ hipError_t launch_toeplitz(const RssParams &p0, int num_cus, hipStream_t st)
 #else
 		(void)var;
 		(void)depth;
-		CGCK_RSS_AB(12); // the measured default; the other depths and forms are lab builds
+		CGCK_RSS_AB(kRssX4Depth); // the measured default; the other depths and forms are lab builds
 #endif
 #undef CGCK_RSS_AB
 #if CGCK_LAB
@@ -362,7 +362,7 @@ hipError_t launch_toeplitz(const RssParams &p0, int num_cus, hipStream_t st)
 		p.n -= ng * 4;
 	}
 	const uint64_t want = (p.n + 255) / 256;
-	const uint64_t cap = (uint64_t)num_cus * 8;
+	const uint64_t cap = (uint64_t)num_cus * kRssPassBlocksPerCu;
 	const dim3 g((unsigned)(want < cap ? want : cap)), b(256);
 	const bool aligned = ((uintptr_t)p.data & 3) == 0 && (p.stride & 3) == 0;
 	const bool lds = p.cnt <= kRssLdsMaxCnt;

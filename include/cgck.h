@@ -1210,6 +1210,12 @@ int cgck_test_pcb_pass(cgck_ctx_t *ctx, uint64_t *frames);
  * Bit 1: the A/B's other table shape, 4-byte slots that hold the index alone (pcbb_kernel<false>,
  * pcbl_kernel<.., false>).  Returns the previous value; -EINVAL outside 0..3. */
 int cgck_test_pcb_mode(int mode);
+/* cgck_toeplitz's launch geometry on ctx's device.  records: what one pass of the
+ * per-record kernel's grid covers (its workgroup cap, eight per compute unit, x 256);
+ * a batch above twice that makes every lane run three passes.  groups: the 4-record
+ * groups the dense kernel's register ring holds before it wraps (its workgroups x 256
+ * lanes x the ring depth).  -EINVAL: a NULL ctx, records or groups. */
+int cgck_test_rss_pass(cgck_ctx_t *ctx, uint64_t *records, uint64_t *groups);
 
 #ifdef __cplusplus
 }
