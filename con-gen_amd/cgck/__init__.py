@@ -165,6 +165,57 @@ class PcbRes(ctypes.Structure):
                 ("count", ctypes.c_void_p)]
 
 
+# cgck_l4_reply: the class in the low nibble of cls[k] (cgck_l4_build's in.cls: RPL_RST
+# is SEG_TCP, every other class one the builder skips), the family bit beside it, the
+# flags of the call and the running counters.
+RPL_RST, RPL_SKIP, RPL_NOTMISS, RPL_DROPPED, RPL_NONE, RPL_QUIET = 0, 2, 3, 4, 5, 6
+RPL_NCLASS = 7
+RPL_IP6 = 1 << 4
+RPL_NO_RST, RPL_NO_MCAST = 1, 2
+RPL_NCOUNT = 8          # [class] for the seven class values, [7] RSTs on IPv6 frames
+L4R_STORE_DEFAULT, L4R_STORE_OWN, L4R_STORE_TURNED = 0, 1, 2
+
+
+class Flow(ctypes.Structure):
+    """cgck_flow_t by value (FLOW_DTYPE's layout): cgck_l4_reply's link template."""
+    _fields_ = [("eth_dst", ctypes.c_uint8 * 6), ("eth_src", ctypes.c_uint8 * 6), ("vlan_tci", ctypes.c_uint16),
+                ("flags", ctypes.c_uint8), ("ttl", ctypes.c_uint8), ("laddr", ctypes.c_uint8 * 16),
+                ("faddr", ctypes.c_uint8 * 16)]
+
+    @classmethod
+    def of(cls, rec):
+        """From a FLOW_DTYPE record, a Flow, or None (all zero)."""
+        if isinstance(rec, cls):
+            return rec
+        f = cls()
+        if rec is not None:
+            raw = np.asarray(rec, FLOW_DTYPE).reshape(1).view(np.uint8)
+            ctypes.memmove(ctypes.byref(f), raw.ctypes.data, 48)
+        return f
+
+
+assert ctypes.sizeof(Flow) == 48
+
+
+class L4ReplyIn(ctypes.Structure):
+    """cgck_l4_reply_in_t: the received burst, the selectors and the link template."""
+    _fields_ = [("desc", ctypes.c_void_p), ("seg", ctypes.c_void_p), ("cls", ctypes.c_void_p),
+                ("kind", ctypes.c_void_p), ("verdict", ctypes.c_void_p), ("l2cls", ctypes.c_void_p),
+                ("at", ctypes.c_void_p), ("link", Flow), ("vmask", ctypes.c_uint8), ("flags", ctypes.c_uint32)]
+
+
+class L4ReplyRes(ctypes.Structure):
+    """cgck_l4_reply_res_t: the optional outputs of the reply rule."""
+    _fields_ = [("seg", ctypes.c_void_p), ("flow", ctypes.c_void_p), ("cls", ctypes.c_void_p),
+                ("queue", ctypes.c_void_p), ("count", ctypes.c_void_p)]
+
+
+class L4ReplyPack(ctypes.Structure):
+    """cgck_l4_reply_pack_t: the caller's intermediates of cgck_l4_reply_packed."""
+    _fields_ = [("queue", ctypes.c_void_p), ("at", ctypes.c_void_p), ("qoff", ctypes.c_void_p),
+                ("work", ctypes.c_void_p)]
+
+
 class SteerRes(ctypes.Structure):
     """cgck_steer_res_t: the optional outputs of the partition by queue id."""
     _fields_ = [("qoff", ctypes.c_void_p), ("perm", ctypes.c_void_p), ("slot", ctypes.c_void_p),
@@ -196,6 +247,7 @@ EXPORTS = (
     "cgck_l4_build", "cgck_l4_build_hdr_bytes", "cgck_test_l4_build_pass", "cgck_test_l4_build_store",
     "cgck_pcb_table_bytes", "cgck_pcb_build", "cgck_pcb_lookup", "cgck_test_pcb_pass", "cgck_test_pcb_mode",
     "cgck_test_rss_pass",
+    "cgck_l4_reply", "cgck_l4_reply_packed", "cgck_l4_reply_rule", "cgck_test_l4_reply_pass", "cgck_test_l4_reply_store",
 )
 # Descriptor layout hint (cgck_set_desc_layout)
 LAYOUT_ANY = 0
@@ -311,6 +363,14 @@ def bind(path):
         L.cgck_pcb_lookup.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, ctypes.POINTER(Pcb), ctypes.POINTER(PcbRes), _vp]
         L.cgck_test_pcb_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
         L.cgck_test_pcb_mode.argtypes = [ctypes.c_int]
+    if hasattr(L, "cgck_l4_reply"):            # tcp_respond's RSTs (an older build loads without them)
+        _rin, _rres = ctypes.POINTER(L4ReplyIn), ctypes.POINTER(L4ReplyRes)
+        L.cgck_l4_reply.argtypes = [_vp, _vp, _u64, _rin, _rres, _vp]
+        L.cgck_l4_reply_packed.argtypes = [_vp, _vp, _u64, _rin, _rres, ctypes.POINTER(L4ReplyPack), _vp]
+        L.cgck_l4_reply_rule.argtypes = [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8,
+                                         _u32, _vp, _u32, ctypes.POINTER(Flow), _vp, _vp]
+        L.cgck_test_l4_reply_pass.argtypes = [_vp, ctypes.POINTER(_u64)]
+        L.cgck_test_l4_reply_store.argtypes = [ctypes.c_int]
     if hasattr(L, "cgck_test_rss_pass"):       # cgck_toeplitz's geometry (an older build loads without it)
         L.cgck_test_rss_pass.argtypes = [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]
     L.cgck_dst_cache.argtypes = [_vp, ctypes.POINTER(DstParams), _vp, _u32, _vp, _vp]
@@ -407,6 +467,27 @@ def pcb_mode(mode):
     (PCB_MODE_UNTAGGED) of every later pcb_build and pcb_lookup of the process;
     returns the previous value."""
     return _check(load().cgck_test_pcb_mode(mode), "cgck_test_pcb_mode")
+
+
+def l4_reply_store(shape):
+    """cgck_test_l4_reply_store: pin how l4r_kernel stores seg and flow under `at` for
+    the process (L4R_STORE_*); returns the previous value."""
+    return _check(load().cgck_test_l4_reply_store(shape), "cgck_test_l4_reply_store")
+
+
+def l4_reply_rule(seg, ip, link, cls=SEG_TCP, kind=PCB_MISS, verdict=0, vmask=0, l2cls=0, flags=0, ip_len=None):
+    """cgck_l4_reply_rule: the reply rule for one frame in host memory.  seg: a
+    SEG_DTYPE record; ip: the frame's bytes from the IP header on (uint8 array; ip_len
+    defaults to all of it); link: a FLOW_DTYPE record or Flow.  Returns (class byte,
+    reply SEG_DTYPE record, reply FLOW_DTYPE record).  No device, no context."""
+    s = np.array(seg, SEG_DTYPE).reshape(1)
+    b = np.ascontiguousarray(ip, np.uint8)
+    r, f = np.zeros(1, SEG_DTYPE), np.zeros(1, FLOW_DTYPE)
+    lk = Flow.of(link)
+    c = _check(load().cgck_l4_reply_rule(s.ctypes.data, cls, kind, verdict, vmask, l2cls, flags,
+                                         b.ctypes.data if len(b) else None, len(b) if ip_len is None else ip_len,
+                                         ctypes.byref(lk), r.ctypes.data, f.ctypes.data), "cgck_l4_reply_rule")
+    return c, r[0], f[0]
 
 
 def _u8(a):
@@ -897,6 +978,43 @@ class Engine:
         """cgck_test_pcb_pass: frames one pass of pcbl_kernel's grid covers on this device."""
         f = _u64(0)
         _check(load().cgck_test_pcb_pass(self.ctx, ctypes.byref(f)), "cgck_test_pcb_pass")
+        return f.value
+
+    @staticmethod
+    def _l4_reply_args(desc, seg, link, cls, kind, verdict, l2cls, at, vmask, flags, seg_out, flow_out, cls_out,
+                       queue, count):
+        arg = L4ReplyIn(desc, seg, cls, kind, verdict, l2cls, at, Flow.of(link), vmask, flags)
+        return arg, L4ReplyRes(seg_out, flow_out, cls_out, queue, count)
+
+    def l4_reply(self, base, n, desc, seg, link, cls=None, kind=None, verdict=None, l2cls=None, at=None, vmask=0,
+                 flags=0, seg_out=None, flow_out=None, cls_out=None, queue=None, count=None, stream=None):
+        """cgck_l4_reply: tcp_respond's RST records for the n received frames desc and
+        seg (cgck_l4_desc's records) describe; device pointers or None (cls: every
+        frame TCP; kind: every frame a MISS; verdict, l2cls: 0; at: frame k's outputs go
+        to index k).  link: a FLOW_DTYPE record or Flow, the replies' link header.  Each
+        output is optional (seg_out: SEG_DTYPE[n]; flow_out: FLOW_DTYPE[n]; cls_out,
+        queue: u8[n]; count: u32[RPL_NCOUNT], accumulated).  Asynchronous."""
+        arg, res = self._l4_reply_args(desc, seg, link, cls, kind, verdict, l2cls, at, vmask, flags, seg_out, flow_out,
+                                       cls_out, queue, count)
+        _check(load().cgck_l4_reply(self.ctx, base, n, ctypes.byref(arg), ctypes.byref(res), stream), "cgck_l4_reply")
+
+    def l4_reply_packed(self, base, n, desc, seg, link, pk_queue, pk_at, pk_qoff, work=None, cls=None, kind=None,
+                        verdict=None, l2cls=None, vmask=0, flags=0, seg_out=None, flow_out=None, cls_out=None,
+                        queue=None, count=None, stream=None):
+        """cgck_l4_reply_packed: the RSTs first and in arrival order (the reference's
+        slot and ip_id order).  pk_queue: u8[n], pk_at: u32[n], pk_qoff: u32[3] (qoff[1]
+        = the number of RSTs), work: steer_work_bytes(n, 1) bytes or None; the rest as
+        l4_reply.  Asynchronous."""
+        arg, res = self._l4_reply_args(desc, seg, link, cls, kind, verdict, l2cls, None, vmask, flags, seg_out, flow_out,
+                                       cls_out, queue, count)
+        pk = L4ReplyPack(pk_queue, pk_at, pk_qoff, work)
+        _check(load().cgck_l4_reply_packed(self.ctx, base, n, ctypes.byref(arg), ctypes.byref(res), ctypes.byref(pk),
+                                           stream), "cgck_l4_reply_packed")
+
+    def l4_reply_pass_frames(self):
+        """cgck_test_l4_reply_pass: frames one pass of l4r_kernel's grid covers on this device."""
+        f = _u64(0)
+        _check(load().cgck_test_l4_reply_pass(self.ctx, ctypes.byref(f)), "cgck_test_l4_reply_pass")
         return f.value
 
     def synth_eth(self, base, desc, raw, n, vlan_every, seed, stream=None):

@@ -22,6 +22,7 @@
 
 #include "cgck_host.h"
 #include "cgck_pcb_probe.h"
+#include "cgck_reply_rule.h"
 #include "cgck_steer_plan.h"
 
 using namespace cgck;
@@ -1368,6 +1369,124 @@ extern "C" int cgck_test_pcb_mode(int mode)
 	if (mode < 0 || mode > 3)
 		return set_err(-EINVAL, "cgck_test_pcb_mode: mode must be within 0..3");
 	return g_pcb_mode.exchange(mode, std::memory_order_relaxed);
+}
+
+// tcp_respond's RSTs for a burst (cgck_l4r.hip): one launch, no scratch.  Under
+// `at` the store shape is the product's (kL4rTurned) unless cgck_test_l4_reply_store
+// pinned one.
+static constexpr bool kL4rTurned = false; // the A/B of DESIGN.md §5.16
+static std::atomic<int> g_l4r_store{0};
+
+// The argument rules cgck_l4_reply and cgck_l4_reply_packed share; `what` names the
+// caller in the message.
+static int l4r_check(const char *what, const cgck_ctx *c, const void *base, uint64_t n, const cgck_l4_reply_in_t *in,
+		     const cgck_l4_reply_res_t *res)
+{
+	if (!c || !base || !in || !res)
+		return set_err(-EINVAL, "%s: NULL context, base, in or res", what);
+	if (n && (!in->desc || !in->seg))
+		return set_err(-EINVAL, "%s: NULL descriptors or seg", what);
+	if (!res->seg && !res->flow && !res->cls && !res->queue && !res->count)
+		return set_err(-EINVAL, "%s: every output is NULL", what);
+	if (((uintptr_t)in->desc & 3) != 0 || ((uintptr_t)in->at & 3) != 0 || ((uintptr_t)res->count & 3) != 0)
+		return set_err(-EINVAL, "%s: desc, at and count must be 4-byte aligned", what);
+	if (((uintptr_t)in->seg & 15) != 0 || ((uintptr_t)res->seg & 15) != 0 || ((uintptr_t)res->flow & 15) != 0)
+		return set_err(-EINVAL, "%s: seg and flow must be 16-byte aligned", what);
+	if (in->link.flags & ~kRplLinkBits)
+		return set_err(-EINVAL, "%s: link.flags 0x%02x has a bit outside CGCK_FLOW_IP6 | CGCK_FLOW_VLAN", what,
+			       in->link.flags);
+	if (in->flags & ~kRplFlags)
+		return set_err(-EINVAL, "%s: flags 0x%x has an unknown bit", what, in->flags);
+	if (res->seg && res->seg == in->seg)
+		return set_err(-EINVAL, "%s: the output seg must not be the input seg", what);
+	return 0;
+}
+
+static int l4r_run(cgck_ctx *c, const void *base, uint64_t n, const cgck_l4_reply_in_t *in, const uint32_t *at,
+		   const cgck_l4_reply_res_t *res, hipStream_t st)
+{
+	L4rParams p = {};
+	p.base = (const uint8_t *)base;
+	p.desc = in->desc;
+	p.seg = in->seg;
+	p.cls = in->cls;
+	p.kind = in->kind;
+	p.verdict = in->verdict;
+	p.l2cls = in->l2cls;
+	p.at = at;
+	p.n = n;
+	p.zero = c->d_zero;
+	memcpy(p.link, &in->link, sizeof(p.link));
+	p.vmask = in->vmask;
+	p.flags = in->flags;
+	p.seg_out = res->seg;
+	p.flow_out = res->flow;
+	p.cls_out = res->cls;
+	p.queue = res->queue;
+	p.count = res->count;
+	const int shape = g_l4r_store.load(std::memory_order_relaxed);
+	HIP_TRY(launch_l4r(p, shape == 0 ? kL4rTurned : shape == 2, c->num_cus, st));
+	c->last_kernel = t_kernel;
+	return 0;
+}
+
+extern "C" int cgck_l4_reply(cgck_ctx_t *c, const void *base, uint64_t n, const cgck_l4_reply_in_t *in,
+			     const cgck_l4_reply_res_t *res, void *stream)
+{
+	int rc = l4r_check("cgck_l4_reply", c, base, n, in, res);
+	if (rc)
+		return rc;
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	return l4r_run(c, base, n, in, in->at, res, pick(c, stream));
+}
+
+// cgck_l4_reply for the queue bytes, cgck_steer with one queue over them, then
+// cgck_l4_reply at the slots the steer gave, on one stream.
+extern "C" int cgck_l4_reply_packed(cgck_ctx_t *c, const void *base, uint64_t n, const cgck_l4_reply_in_t *in,
+				    const cgck_l4_reply_res_t *res, const cgck_l4_reply_pack_t *pk, void *stream)
+{
+	int rc = l4r_check("cgck_l4_reply_packed", c, base, n, in, res);
+	if (rc)
+		return rc;
+	if (!pk || !pk->queue || !pk->at || !pk->qoff)
+		return set_err(-EINVAL, "cgck_l4_reply_packed: NULL pk, queue, at or qoff");
+	if (in->at)
+		return set_err(-EINVAL, "cgck_l4_reply_packed: in->at must be NULL (the call computes it into pk->at)");
+	if (((uintptr_t)pk->at & 3) != 0 || ((uintptr_t)pk->qoff & 3) != 0)
+		return set_err(-EINVAL, "cgck_l4_reply_packed: at and qoff must be 4-byte aligned");
+	cgck_steer_res_t sres = {};
+	sres.qoff = pk->qoff;
+	sres.slot = pk->at;
+	if ((rc = steer_check("cgck_l4_reply_packed", c, pk->queue, n, 1, nullptr, &sres, pk->work)))
+		return rc;
+	if (n == 0)
+		return 0;
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = pick(c, stream);
+	cgck_l4_reply_res_t first = {};
+	first.queue = pk->queue;
+	if ((rc = l4r_run(c, base, n, in, nullptr, &first, st)))
+		return rc;
+	if ((rc = steer_run(c, pk->queue, n, 1, nullptr, &sres, pk->work, st)))
+		return rc;
+	return l4r_run(c, base, n, in, pk->at, res, st);
+}
+
+extern "C" int cgck_test_l4_reply_pass(cgck_ctx_t *c, uint64_t *frames)
+{
+	if (!c || !frames)
+		return set_err(-EINVAL, "cgck_test_l4_reply_pass: NULL argument");
+	*frames = frame_pass_frames(c->num_cus);
+	return 0;
+}
+
+extern "C" int cgck_test_l4_reply_store(int shape)
+{
+	if (shape < 0 || shape > 2)
+		return set_err(-EINVAL, "cgck_test_l4_reply_store: shape must be 0 (the product's), 1 (own lanes) or 2 (turned)");
+	return g_l4r_store.exchange(shape, std::memory_order_relaxed);
 }
 
 extern "C" int cgck_dst_cache(cgck_ctx_t *c, const cgck_dst_params_t *prm, cgck_dst_entry_t *out, uint32_t cap,

@@ -279,8 +279,32 @@ struct PcblParams {
 hipError_t launch_pcbb(const PcbbParams &p, bool tagged, hipStream_t st);
 hipError_t launch_pcbl(const PcblParams &p, bool tagged, int num_cus, hipStream_t st);
 
+// tcp_respond's RSTs for a burst (cgck_l4r.hip; include/cgck.h, section 3).  desc,
+// seg: the burst; the four selectors, at and each output may be nullptr.  link: the
+// first four dwords of the caller's flow template (MACs, vlan_tci, flags, ttl).
+struct L4rParams {
+	const uint8_t *base;
+	const void *desc;
+	const void *seg;
+	const uint8_t *cls, *kind, *verdict, *l2cls;
+	const uint32_t *at;
+	uint64_t n;
+	const void *zero;
+	uint32_t link[4];
+	uint32_t vmask, flags;
+	void *seg_out;
+	void *flow_out;
+	uint8_t *cls_out;
+	uint8_t *queue;
+	uint32_t *count;
+};
+
+// turned: under `at`, seg and flow leave turned through LDS (l4r_kernel<.., 2>), else
+// from their own lanes (<.., 1>); without `at` they always leave turned (<.., 0>).
+hipError_t launch_l4r(const L4rParams &p, bool turned, int num_cus, hipStream_t st);
+
 // Frames that the workgroups one launch of rssf_kernel, l2d_kernel, l4d_kernel,
-// l4b_kernel or pcbl_kernel runs at most cover per pass (cgck_frame.h).
+// l4b_kernel, pcbl_kernel or l4r_kernel runs at most cover per pass (cgck_frame.h).
 uint64_t frame_pass_frames(int num_cus);
 hipError_t launch_l4d(const L4dParams &p, int num_cus, hipStream_t st);
 // turned: the header's whole 16-byte granules leave through LDS (l4b_kernel<.., true>)

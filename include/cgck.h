@@ -1095,6 +1095,134 @@ int cgck_pcb_lookup(cgck_ctx_t *ctx, const void *base, const cgck_desc_t *desc, 
 		    const uint8_t *cls /* or NULL: every frame TCP */, uint64_t n,
 		    const cgck_pcb_t *pcb, const cgck_pcb_res_t *res, void *stream);
 
+/* The first reply either stack sends: tcp_respond's RST for a TCP segment that
+ * found no PCB (bsd44/tcp_input.c:128-129, 881-899; tcp_subr.c:93-123), for a whole
+ * burst on the device.  cgck_l4_desc's records, cgck_pcb_lookup's kinds and the
+ * verify's verdicts go in; the segment records and the flow records that
+ * cgck_l4_build takes come out, so no host pass over frame bytes lies between the
+ * receive burst and the transmit burst.  A MISS frame has fidx = 0xFFFFFFFF: no
+ * entry of the caller's flow[] fits it, and its reply's addresses are the received
+ * frame's, swapped, which is why this call reads the frames.  The rule is stateless:
+ * with tp == NULL tcp_respond reads nothing but the received segment.  Everything
+ * with tp != NULL (keepalives, ACKs, which segment to send) stays the caller's
+ * (DESIGN.md §6).
+ *
+ * Contract, total over every input byte string.  For frame k: s = seg[k]; c = cls ?
+ * cls[k] & 15 : CGCK_SEG_TCP; kd = kind ? kind[k] : CGCK_PCB_MISS; vd = verdict ?
+ * verdict[k] : 0; lc = l2cls ? l2cls[k] : 0; b the ip_len bytes at base + frame_off +
+ * l3_off; v = b[0] >> 4.  The class, by these rules in order:
+ *  1. c != CGCK_SEG_TCP: SKIP.  (A UDP miss draws icmp_error's port unreachable,
+ *     which cgck_l4_build cannot build: it stays the caller's.)
+ *  2. kd != CGCK_PCB_MISS: NOTMISS.
+ *  3. vd & vmask: DROPPED.  vmask is the caller's checksum policy: CGCK_BAD_LEN,
+ *     with CGCK_BAD_IP when t_ip_do_incksum != 0 (ip_input.c:50-57 returns on a bad
+ *     sum) and CGCK_BAD_L4 when t_tcp_do_incksum > 1 (tcp_input.c:77-85 drops only
+ *     then; at 1 it counts the bad sum and goes on).
+ *  4. cgck_pcb_lookup's rule 2, word for word: NONE when ip_len == 0, when v == 4
+ *     with ip_len < 20, when v == 6 with ip_len < 40, and for any other v.  ip_len
+ *     bounds every read; the header's own length fields are not consulted.
+ *  5. QUIET with flags & CGCK_RPL_NO_RST and s.th_flags & 0x04; and with flags &
+ *     CGCK_RPL_NO_MCAST when lc & (CGCK_L2_BCAST | CGCK_L2_MCAST), or v == 4 with
+ *     (b[16] >> 4) == 14, or v == 6 with b[24] == 0xFF.  This is 4.4BSD's test, which
+ *     the reference has commented out (tcp_input.c:887-890): with flags == 0 the call
+ *     is the reference's behaviour and answers an RST with an RST.
+ *  6. RST.
+ * The reply record r of an RST is zero except: r.sport = s.dport and r.dport =
+ * s.sport, as stored; with s.th_flags & 0x10, r.seq = s.ack and r.th_flags = 0x04;
+ * otherwise r.ack = s.seq + s.pay_len + (s.th_flags & 0x02 ? 1 : 0) modulo 2^32 and
+ * r.th_flags = 0x14.  win, opt and pay_len are 0 (tcp_subr.c:115-116).
+ * The reply flow f of an RST: eth_dst, eth_src, vlan_tci and ttl are link's (the
+ * reference sends from its configured MACs, ip_output.c:67-68, not the frame's
+ * swapped ones); flags = (link.flags & CGCK_FLOW_VLAN) | (v == 6 ? CGCK_FLOW_IP6 :
+ * 0); laddr = the frame's destination (v4: b[16..20) and twelve zero bytes, v6:
+ * b[24..40)); faddr = its source (b[12..16) or b[8..24)).
+ * Every other class yields an all-zero r and f.
+ * The class byte is class | CGCK_RPL_IP6, the flag set whenever ip_len > 0 and v ==
+ * 6.  It is cgck_l4_build's in.cls: CGCK_RPL_RST == CGCK_SEG_TCP, every other class
+ * is one its rule 1 skips, and the flag is CGCK_SEG_IP6.
+ *
+ * Outputs.  seg, flow and cls are indexed by a = at ? at[k] : k; a frame with a >= n
+ * writes none of the three and is still counted.  Two frames with one `at` value
+ * are the caller's error: which of them lands is unspecified, as for overlapping
+ * slots in cgck_l4_build.  queue[k] (always at k) = 0 for an RST and 0xFF otherwise:
+ * cgck_steer's input with queue_num 1.  count[class] += 1 per frame and count[7] +=
+ * 1 per RST on an IPv6 frame (count[1] stays: no class has that value).
+ *
+ * cgck_l4_reply_packed: the replies in the reference's slot and id order.  The
+ * reference hands out one transmit slot and one ip_id per packet sent (tx_alloc,
+ * ip_output.c:40,52), not per packet received.  On one stream: cgck_l4_reply with
+ * queue = pk->queue alone; cgck_steer(pk->queue, n, 1, NULL, {qoff = pk->qoff, slot =
+ * pk->at}, pk->work); cgck_l4_reply with in.at = pk->at and the caller's res, whose
+ * counters are therefore counted once.  Afterwards qoff[1] = R, the number of RSTs;
+ * seg[0..R) and flow[0..R) are the RSTs in arrival order; cls[R..n) holds the other
+ * classes, and seg and flow there are zero.  A cgck_l4_build over n with fidx = NULL,
+ * in.cls = cls and ip_id0 fills slots 0..R-1 with ids ip_id0 + r, as tcp_respond
+ * would, and skips the rest; a caller that has read qoff[1] builds over R.  The
+ * caller owns pk's arrays: queue u8[n], at u32[n], qoff u32[3], work of
+ * cgck_steer_work_bytes(n, 1) bytes (0 up to 4096 frames: work may then be NULL).
+ * in->at must be NULL.
+ *
+ * cgck_l4_reply_rule: the rule for one frame in host memory; the same source text
+ * as the kernel's.  Returns the class byte and fills *r and *f.  Pure: no device,
+ * no context.  It is what a host-resident burst uses.  -EINVAL: a NULL s, link, r
+ * or f, a NULL ip with ip_len > 0, and the flags and link.flags cgck_l4_reply
+ * refuses.
+ *
+ * Execution.  Asynchronous on `stream` (NULL: the context's).  n == 0 returns 0,
+ * launches nothing and writes nothing.  The inputs and the frames are never
+ * written.  The library keeps no scratch.  One kernel, l4r_kernel, a lane per
+ * frame; every read of a frame lies inside the 16-byte granules that hold a byte
+ * of [frame, frame + ip_len) (cgck_rss_desc's rule); plain vector stores; no lane
+ * or workgroup waits for another.  DESIGN.md §5.16 has the design.
+ * -EINVAL: a NULL ctx, base, in or res; with n > 0 a NULL desc or seg; every output
+ * NULL; a desc, at or count that is not 4-byte aligned, a seg or flow (on either
+ * side) that is not 16-byte aligned; link.flags with a bit outside CGCK_FLOW_IP6 |
+ * CGCK_FLOW_VLAN (the template's IP6 bit is ignored); flags with an unknown bit; an
+ * output seg equal to the input seg.  The packed form adds: a NULL pk, queue, at or
+ * qoff; a non-NULL in->at; a misaligned at, qoff or work; n above 0xFFFFFFFF; a NULL
+ * work while cgck_steer_work_bytes(n, 1) != 0.  The argument checks come before any
+ * device work.
+ * Out of scope: ICMP unreachables for UDP misses and echo replies
+ * (the builder has no ICMP); replies on a live connection; a strided form. */
+enum { CGCK_RPL_RST = 0, CGCK_RPL_SKIP = 2, CGCK_RPL_NOTMISS = 3, CGCK_RPL_DROPPED = 4, CGCK_RPL_NONE = 5,
+       CGCK_RPL_QUIET = 6, CGCK_RPL_NCLASS = 7 };              /* low nibble of cls[k]; 1 is no class */
+enum { CGCK_RPL_IP6 = 1u << 4 };                               /* flag bit of cls[k] */
+enum { CGCK_RPL_NO_RST = 1, CGCK_RPL_NO_MCAST = 2 };           /* flags */
+#define CGCK_RPL_NCOUNT 8       /* [class] for the seven class values, [7] RSTs on IPv6 frames */
+
+typedef struct cgck_l4_reply_in {       /* pointers are device memory */
+	const cgck_desc_t *desc;            /* [n] the received frames */
+	const cgck_seg_t  *seg;             /* [n] cgck_l4_desc's records, 16-byte aligned */
+	const uint8_t *cls, *kind, *verdict, *l2cls;   /* [n] each, or NULL (see the rule) */
+	const uint32_t *at;                 /* [n] or NULL: frame k's outputs go to index at[k] (NULL: k) */
+	cgck_flow_t link;                   /* by value, host memory: MACs, vlan_tci, flags & VLAN, ttl */
+	uint8_t vmask;
+	uint32_t flags;                     /* CGCK_RPL_NO_RST | CGCK_RPL_NO_MCAST */
+} cgck_l4_reply_in_t;
+
+typedef struct cgck_l4_reply_res {      /* device memory; each optional; at least one non-NULL */
+	cgck_seg_t  *seg;                   /* [n], 16-byte aligned */
+	cgck_flow_t *flow;                  /* [n], 16-byte aligned: cgck_l4_build's flow with fidx NULL */
+	uint8_t     *cls;                   /* [n] class | CGCK_RPL_IP6: cgck_l4_build's in.cls */
+	uint8_t     *queue;                 /* [n] 0 for an RST, 0xFF otherwise: cgck_steer's input, queue_num 1 */
+	uint32_t    *count;                 /* u32[CGCK_RPL_NCOUNT] running counters (+=) */
+} cgck_l4_reply_res_t;
+
+typedef struct cgck_l4_reply_pack {     /* device memory, the caller's; cgck_l4_reply_packed's intermediates */
+	uint8_t  *queue;                    /* [n] */
+	uint32_t *at;                       /* [n] the slot of frame k: RSTs first, in arrival order */
+	uint32_t *qoff;                     /* u32[3], written: {0, R, n} */
+	void     *work;                     /* cgck_steer_work_bytes(n, 1) bytes, or NULL when that is 0 */
+} cgck_l4_reply_pack_t;
+
+int cgck_l4_reply(cgck_ctx_t *ctx, const void *base, uint64_t n, const cgck_l4_reply_in_t *in,
+		  const cgck_l4_reply_res_t *res, void *stream);
+int cgck_l4_reply_packed(cgck_ctx_t *ctx, const void *base, uint64_t n, const cgck_l4_reply_in_t *in,
+			 const cgck_l4_reply_res_t *res, const cgck_l4_reply_pack_t *pk, void *stream);
+int cgck_l4_reply_rule(const cgck_seg_t *s, uint8_t cls, uint8_t kind, uint8_t verdict, uint8_t vmask,
+		       uint8_t l2cls, uint32_t flags, const uint8_t *ip, uint32_t ip_len, const cgck_flow_t *link,
+		       cgck_seg_t *r, cgck_flow_t *f);
+
 /* One dst-cache entry: the fields thread_init_dst_cache fills in struct
  * ip_socket (con-gen.c:344-349; subr.h:218-228).  16 bytes. */
 typedef struct cgck_dst_entry {
@@ -1210,6 +1338,15 @@ int cgck_test_pcb_pass(cgck_ctx_t *ctx, uint64_t *frames);
  * Bit 1: the A/B's other table shape, 4-byte slots that hold the index alone (pcbb_kernel<false>,
  * pcbl_kernel<.., false>).  Returns the previous value; -EINVAL outside 0..3. */
 int cgck_test_pcb_mode(int mode);
+/* The same as cgck_test_l4_pass for cgck_l4_reply's grid. */
+int cgck_test_l4_reply_pass(cgck_ctx_t *ctx, uint64_t *frames);
+/* Pin how l4r_kernel stores seg and flow under `at` for every later cgck_l4_reply of the process (the
+ * tests of both shapes and the A/B of tools/l4r_ab.py): 0 the product's choice, 1 a lane
+ * stores its own 16-byte pieces (l4r_kernel<.., 1>), 2 the pieces and their targets are turned through
+ * LDS so that one store instruction covers whole records of consecutive frames (l4r_kernel<.., 2>).
+ * Without `at` the records always leave turned, as consecutive pieces.  Returns the previous value;
+ * -EINVAL for any other. */
+int cgck_test_l4_reply_store(int shape);
 /* cgck_toeplitz's launch geometry on ctx's device.  records: what one pass of the
  * per-record kernel's grid covers (its workgroup cap, eight per compute unit, x 256);
  * a batch above twice that makes every lane run three passes.  groups: the 4-record
